@@ -13,6 +13,13 @@ does it (RelationTripleEpochs.run_steps -> oea_triple_epoch_range: ONE C call pe
 and negatives on a side stream).  value = positives (training triples) consumed per second, whole job.
 
   python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong] [--exchange step|epoch|allreduce]
+                  [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set-up, W warm-up steps, the K timed steps, the result line.  --full adds everything
+else listed under OUTPUT below (kernel-timed roofline, counter passes, CPU baseline, eval / neighbour / 15K-shape / GNN legs,
+the side legs at N > 1).  --dump-outputs DIR writes, after the timed steps, what their last step left the caller (the trained
+tables and their Adagrad state on a fixed, seeded sample of entity rows, the loss sum) as DIR/<name>.npy; the inputs are the
+same from run to run (seeded synthetic KGs, tables and negative streams), so two builds can be compared output for output.
 
 N > 1: `python bench.py --gpus N` launches its own N ranks (torch.distributed.run on 127.0.0.1, one process per GPU,
 RCCL); started under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.  The batch of 20,000 stays GLOBAL (STRONG
@@ -20,17 +27,18 @@ scaling: every rank scores 20,000 / N positives of every batch) with the PARITY-
 rows owned by id mod N; the N-rank job equals the single-GPU job) moving only the BOUNDARY rows a step's batch refers to
 (--exchange halo: all-to-all of the gradient rows to their owners, all-to-all of the rows the next step reads; --exchange step
 = the dense reduce-scatter / all-gather of every owned row, a side leg), one C call per epoch over the C ABI's RCCL
-communicator (oea_triple_epoch_range_halo), with HIP-event phase times.  The same configuration on ONE GPU is timed in the same run
-(extra.single_gpu_same_config).  --exchange epoch (local SGD, one exchange per epoch: drifts from the single-GPU job,
+communicator (oea_triple_epoch_range_halo).  With --full: HIP-event phase times, and the same configuration on ONE GPU timed in
+the same run (extra.single_gpu_same_config).  --exchange epoch (local SGD, one exchange per epoch: drifts from the single-GPU job,
 tests/test_dist_gpu.py) and --scaling weak are named side legs.
 
-Timing: W untimed warm-up steps, then the K-step region -- barrier + synchronize on both sides, MAX over ranks --
-is timed --repeats times (default 50) and the MEDIAN region is reported (a single region is a few ms at this shape: one
-sample of it says little).
+Timing: one untimed epoch and W untimed warm-up steps, then the K-step region -- barrier + synchronize on both sides, MAX
+over ranks -- is timed --repeats times (default 1: K timed steps; 50 with --full) and the MEDIAN region is reported
+(ms_per_step = that region / K).
 
-OUTPUT.  The LAST line of stdout (rank 0) is ONE compact JSON object of at most 4 KB: the contract's keys, `roofline`
-(triple_wave, the scoring kernel of the step: HIP events on its dispatches, design bytes, counter traffic), `roofline_eval`, `cpu_baseline` and a few dozen
-scalars under `extra`.  Everything else -- per-kernel counter dictionaries, region times, formulas, notes, provenance -- goes
+OUTPUT.  The LAST line of stdout (rank 0) is ONE compact JSON object of at most 4 KB: the contract's keys and, with --full,
+`roofline` (triple_wave, the scoring kernel of the step: HIP events on its dispatches, design bytes, counter traffic),
+`roofline_eval`, `cpu_baseline` (null in a plain run) and a few dozen scalars under `extra`.  Everything else -- per-kernel
+counter dictionaries, region times, formulas, notes, provenance -- goes
 to bench_detail.json (repo root; also gpurun_out/ when that directory exists), named by the line's `detail` key:
   roofline      dominant kernel (triple_wave, fwd + bwd; triple_grouped under OEA_STEP_WAVE=0), timed live by HIP events attached to its dispatches.
                 `frac` is priced on the bytes the kernel is DESIGNED to move -- it shares the positive's three rows across
@@ -62,14 +70,23 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP64_VALU_PEAK_TOPS = 39.3   # fp64 vector ADD/SUB rate = half of the 78.6 TFLOP/s FMA peak (256 CUs x 64 lanes x 2.4 GHz)
 PROFILE_STRIDE = int(os.environ.get("OEA_BENCH_PROFILE_STRIDE", "1"))   # steps of the kernel-timing regions that carry HIP events
 KERNEL_TIMING_REGIONS = 2
+DUMP_ENT_BYTES = 48 << 20     # --dump-outputs: the entity rows (table + accumulator) written, in bytes; 64 MB in all at most
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (of each region, when --repeats > 1)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=50, help="timed K-step regions (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed K-step regions (median reported); default 1, or 50 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: kernel-timed roofline, counter traffic, CPU baseline, eval / neighbour / "
+                         "15K-shape / GNN legs, the side legs at N > 1 (each can still be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their last step left the caller (trained tables, Adagrad state, "
+                         "loss sum) as DIR/<name>.npy")
     ap.add_argument("--dim", type=int, default=None, help="default: 75 (15K shapes, BASELINE config 2) / 100 (100K shapes)")
     ap.add_argument("--shape", default=None, help="default: EN-FR-100K-V1 at every N (EN-FR-15K-V1 is the side block extra.shape_15k)")
     ap.add_argument("--batch", type=int, default=None,
@@ -110,6 +127,8 @@ def resolve_defaults(args, world):
         args.eps = 0.98 if big else 0.9
     if args.scaling is None:
         args.scaling = "strong" if world > 1 else "weak"
+    if args.repeats is None:
+        args.repeats = 50 if args.full else 1
     return args
 
 
@@ -212,8 +231,9 @@ class Workload:
             dist.barrier()
         self.torch.cuda.synchronize()
 
-    def measure(self, steps, warmup, repeats):
-        """-> dict(times_s [repeats] (max over ranks), pos [repeats] (all ranks), kernel marks)."""
+    def measure(self, steps, warmup, repeats, full=True, outputs=False):
+        """-> dict(times_s [repeats] (max over ranks), pos [repeats] (all ranks); full: kernel marks, touched rows, plan statistics;
+        outputs: what the last timed step left the caller, `outputs` (snapshot_outputs))."""
         torch, ops, ep, tr = self.torch, self.ops, self.epochs, self.trainer
         # priming (untimed, before the W warm-up steps): one whole epoch + its end-of-epoch shuffle, so that the
         # first-use costs of the enqueue path and of the permutation kernels are not inside the timed regions
@@ -235,7 +255,7 @@ class Workload:
             self.barrier()
             return ops.profile_end(4)
         for rep in range(repeats):
-            if rep == repeats // 2:
+            if full and rep == repeats // 2:
                 prof = kernel_timing()
             self.barrier()
             t0 = time.perf_counter()
@@ -243,26 +263,53 @@ class Workload:
             self.barrier()
             times.append(time.perf_counter() - t0)
             pos.append(n)
-        if prof is None:
+        res = {"outputs": self.snapshot_outputs()} if outputs else {}
+        if full and prof is None:
             prof = kernel_timing()
-        (fwd_ms, gap_ms, apply_ms), n_calls = prof
         loss = tr.pop_loss()
         ep.check()
-        touched = self.touched_rows()
-        plan_stats = None
-        try:
-            if getattr(ep, "_plan", None) is not None and getattr(ep, "_plan_ready", False):
-                plan_stats = ops.step_plan_stats(ep._plan, *ep._plan_dims)
-        except Exception as e:      # noqa: BLE001 -- a diagnostic, never the bench line
-            plan_stats = {"error": str(e)[:200]}
+        if full:
+            (fwd_ms, gap_ms, apply_ms), n_calls = prof
+            res.update(fwd_ms=fwd_ms, gap_ms=gap_ms, apply_ms=apply_ms, n_calls=n_calls, touched_rows=self.touched_rows())
+            plan_stats = None
+            try:
+                if getattr(ep, "_plan", None) is not None and getattr(ep, "_plan_ready", False):
+                    plan_stats = ops.step_plan_stats(ep._plan, *ep._plan_dims)
+            except Exception as e:      # noqa: BLE001 -- a diagnostic, never the bench line
+                plan_stats = {"error": str(e)[:200]}
+            res["plan_stats"] = plan_stats
         t = torch.tensor(times, dtype=torch.float64, device=self.ent.var.device)
         c = torch.tensor(pos, dtype=torch.float64, device=self.ent.var.device)
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dist.all_reduce(c, op=dist.ReduceOp.SUM)
-        return dict(times=t.cpu().numpy(), pos=c.cpu().numpy(), pos_local=np.asarray(pos, np.float64),
-                    fwd_ms=fwd_ms, gap_ms=gap_ms, apply_ms=apply_ms, n_calls=n_calls, loss=loss, touched_rows=touched, plan_stats=plan_stats)
+        res.update(times=t.cpu().numpy(), pos=c.cpu().numpy(), pos_local=np.asarray(pos, np.float64), loss=loss)
+        return res
+
+    def snapshot_outputs(self):
+        """what the timed path leaves its caller after its last step -> {name: host float32 / float64 array}: the trained entity
+        table and its Adagrad accumulator on a fixed, seeded sample of rows (the whole table where it fits DUMP_ENT_BYTES; the
+        sampled ids are `ent_rows`), the relation table and its accumulator, and the loss accumulator (sum of the batch losses
+        since the trainer was made, summed over the ranks).  Under the partitioned exchange (N > 1) every rank holds the whole
+        table after a call, but only its own rows of the entity accumulator: that array is left out there."""
+        torch, tr, ent, rel = self.torch, self.trainer, self.ent, self.rel
+        n = ent.visible_rows
+        keep = min(n, DUMP_ENT_BYTES // (2 * 4 * ent.dim))
+        rows = np.arange(n) if keep == n else np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        idx = torch.from_numpy(rows).to(ent.var.device)
+        out = {"ent_rows": rows.astype(np.float64), "ent_embeds": ent.var[idx, :ent.dim].cpu().numpy(),
+               "rel_embeds": rel.var[:rel.visible_rows, :rel.dim].cpu().numpy()}
+        if getattr(tr, "ent_acc", None) is not None and tr.ent_acc.dim() == 2:
+            out["ent_adagrad_acc"] = tr.ent_acc[idx, :ent.dim].cpu().numpy()
+        if getattr(tr, "rel_acc", None) is not None and tr.rel_acc.dim() == 2:
+            out["rel_adagrad_acc"] = tr.rel_acc[:rel.visible_rows, :rel.dim].cpu().numpy()
+        loss = tr.loss.clone()
+        if tr.dist is not None and not tr.replicated:
+            import torch.distributed as dist
+            dist.all_reduce(loss, op=dist.ReduceOp.SUM, group=tr.dist)
+        out["loss_sum"] = loss.cpu().numpy().astype(np.float64)
+        return {k: np.ascontiguousarray(v) for k, v in out.items()}
 
     def touched_rows(self, n_steps=3):
         """entity + relation rows that RECEIVE gradient per step on this rank, counted: after the timed regions a few further steps
@@ -308,12 +355,14 @@ class Workload:
         return out
 
     def summarize(self, m, steps, traffic=None):
-        """median region -> (value, ms_per_step, roofline dict)"""
+        """median region -> (value, ms_per_step, roofline dict; None without the kernel-timing regions of a --full run)"""
         order = np.argsort(m["times"])
         i_med = int(order[len(order) // 2])
         t_med = float(m["times"][i_med])
         value = float(m["pos"][i_med]) / t_med
         ms_per_step = t_med / steps * 1e3
+        if "n_calls" not in m:
+            return value, ms_per_step, None
         d, neg = self.d, self.neg
         launches = max(m["n_calls"], 1)
         pos_per_launch = float(m["pos_local"].mean()) / steps                      # this rank's positives per launch
@@ -398,7 +447,7 @@ def measure_traffic(shape, d, batch, neg, eps, timeout_s=240):
     FETCH_SIZE reports half of the bytes read) over a short run of the same workload: bytes = (2 FETCH + WRITE) * 1024 per
     launch.  Falls back to the committed profile of the same workload (profiles/traffic_<shape>.json)."""
     child = ["--shape", shape, "--dim", str(d), "--batch", str(batch), "--neg", str(neg), "--eps", str(eps), "--steps", "40",
-             "--warmup", "5", "--repeats", "2", "--no-cpu", "--no-extra", "--no-gnn", "--no-traffic"]
+             "--warmup", "5", "--repeats", "2", "--full", "--no-cpu", "--no-extra", "--no-gnn", "--no-traffic"]
     try:
         t0 = time.time()
         fetch, n = _pmc_pass("FETCH_SIZE", child, timeout_s)
@@ -477,17 +526,19 @@ def main():
         return
     wl = Workload(torch, ops, args.shape, args.dim, args.batch, args.neg, args.eps, dev, rank, world, group, args.scaling,
                   args.exchange)
-    m = wl.measure(args.steps, args.warmup, args.repeats)
+    m = wl.measure(args.steps, args.warmup, args.repeats, full=args.full, outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, m.pop("outputs"))
     extra = {}
-    if world > 1:
+    if world > 1 and args.full:
         try:
             extra["exchange_phases"] = wl.phase_times(args.steps)                  # every rank takes part
         except Exception as e:      # noqa: BLE001 -- a side measurement must not take the line down
             extra["exchange_phases"] = {"error": repr(e)[:300]}
-    if not args.no_extra:                   # eval / neighbour legs: row-sharded over the ranks (every rank takes part)
+    if args.full and not args.no_extra:     # eval / neighbour legs: row-sharded over the ranks (every rank takes part)
         extra.update(extra_legs(torch, ops, wl.ent, wl.kgs, args.dim, wl.k1))
     multi = None
-    if world > 1 and not os.environ.get("OEA_BENCH_NO_SIDE"):                     # (OEA_BENCH_NO_SIDE=1: the headline exchange only)
+    if args.full and world > 1 and not os.environ.get("OEA_BENCH_NO_SIDE"):       # (OEA_BENCH_NO_SIDE=1: the headline exchange only)
         multi = multi_gpu_legs(torch, ops, dev, args, rank, world, group, wl)      # every rank takes part
     if rank != 0:
         if world > 1:
@@ -495,7 +546,7 @@ def main():
             dist.barrier()
         return
     traffic = None
-    if world == 1 and not args.no_traffic:
+    if args.full and world == 1 and not args.no_traffic:
         traffic = measure_traffic(args.shape, args.dim, args.batch, args.neg, args.eps)
     value, ms_per_step, roofline = wl.summarize(m, args.steps, traffic)
     extra.update({"neighbour_refresh_first_call_s": round(wl.nbr_first_s, 3), "epoch_loss_sum": m["loss"],
@@ -522,18 +573,18 @@ def main():
         if one:
             extra["speedup_vs_single_gpu_same_config"] = round(value / one["value"], 4)
     cpu = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cpu = cpu_baseline(wl.kgs, args.dim, args, wl.k1, wl.k2)
     big = "100K" in args.shape
     eval_dim = args.dim
-    if not args.no_extra and world == 1 and big and args.dim == 100:
+    if args.full and not args.no_extra and world == 1 and big and args.dim == 100:
         del wl
         torch.cuda.empty_cache()
         try:
             extra["shape_15k"] = side_shape(torch, ops, dev, args, "EN-FR-15K-V1", 75, 5000, 0.9)
         except Exception as e:      # noqa: BLE001 -- a failing side leg must not take the headline line down
             extra["shape_15k"] = {"error": repr(e)[:300]}
-    if not args.no_gnn and world == 1:
+    if args.full and not args.no_gnn and world == 1:
         torch.cuda.empty_cache()
         gtraffic = None if args.no_traffic else measure_gnn_traffic()
         try:
@@ -555,7 +606,7 @@ def main():
             extra["csls_eval_hbm"] = extra["neighbour_search_hbm"] = gtraffic
 
     roofline_eval = eval_roofline(extra, eval_dim)
-    if roofline_eval:
+    if roofline_eval and roofline is not None:
         roofline["eval"] = roofline_eval
     per_gpu = args.batch if args.scaling == "weak" else args.batch / world
     gb = args.batch * world if args.scaling == "weak" else args.batch
@@ -575,7 +626,8 @@ def main():
                    "global_batch": gb, "entities": extra_entities(args.shape),
                    "parallelism": ("dp%d, exchange = %s: %s" % (world, extra.get("exchange_mode"), extra.get("exchange")))
                    if world > 1 else "single",
-                   "timing": "median of %d regions of %d steps, each bracketed by barrier + synchronize" % (args.repeats, args.steps),
+                   "timing": ("median of %d regions of %d steps, each bracketed by barrier + synchronize" % (args.repeats, args.steps)
+                              if args.repeats > 1 else "one region of %d steps, bracketed by barrier + synchronize" % args.steps),
                    "parity_note": "TF1 op semantics / optimiser arithmetic are restated, not executed (no TensorFlow "
                                   "here): SURVEY H1/H3/H4, DESIGN.md section 5"},
         "roofline": roofline, "roofline_eval": roofline_eval, "cpu_baseline": cpu, "extra": extra,
@@ -584,6 +636,17 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one <path>/<name>.npy per array of snapshot_outputs (float32 / float64, DUMP_LIMIT_BYTES in all)"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # bf16 prefilter: three bf16 products per exact product -> the dense bf16 MFMA peak (2.5 PFLOP/s) / 3 per algorithmic flop;
@@ -636,7 +699,7 @@ def _r(v, n=4):
 def compact_line(out, detail_path=None):
     """the contract's keys + roofline + roofline_eval + cpu_baseline + a few dozen scalars of `extra`; everything else (per-kernel
     counter dictionaries, region times, notes, provenance strings) lives in bench_detail.json"""
-    rl = out.get("roofline") or {}
+    rl = out.get("roofline")
     c = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "repeats", "ms_per_step", "higher_is_better",
                              "scaling", "vs_baseline", "dtype", "data") if k in out}
     c["metric"] = "training triples/sec (k=10 truncated negatives + limited loss + Adagrad)"
@@ -644,11 +707,14 @@ def compact_line(out, detail_path=None):
     wl = cfg.get("workload", "")
     c["config"] = {"workload": wl[:200], "global_batch": cfg.get("global_batch"), "entities": cfg.get("entities"),
                    "parallelism": (cfg.get("parallelism") or "")[:60]}
-    r = _pick(rl, ("bound", "achieved", "peak", "unit", "frac", "traffic", "hbm_frac", "avg_kernel_us", "design_bytes_per_launch",
-                   "step_frac", "apply_rows_avg_us", "apply_rows_hbm_frac", "launches_timed"))
-    r["kernel"] = "triple_grouped" if os.environ.get("OEA_STEP_WAVE", "1") == "0" else "triple_wave"
-    r.setdefault("traffic", None)
-    c["roofline"] = r
+    if rl is None:                            # a plain run: no kernel-timing regions (--full)
+        c["roofline"] = None
+    else:
+        r = _pick(rl, ("bound", "achieved", "peak", "unit", "frac", "traffic", "hbm_frac", "avg_kernel_us", "design_bytes_per_launch",
+                       "step_frac", "apply_rows_avg_us", "apply_rows_hbm_frac", "launches_timed"))
+        r["kernel"] = "triple_grouped" if os.environ.get("OEA_STEP_WAVE", "1") == "0" else "triple_wave"
+        r.setdefault("traffic", None)
+        c["roofline"] = r
     re_ = out.get("roofline_eval")
     if re_:
         e = _pick(re_, ("bound", "achieved", "peak", "frac", "pairs_per_s", "speedup_vs_fp32_sweep", "csls10_pairs_per_s",

@@ -269,7 +269,8 @@ def test_bench_two_ranks_like_the_driver(tmp_path, launcher):
     env.pop("WORLD_SIZE", None)
     # the default at every N is the EN-FR-100K-V1 shape; with both ranks on one GPU and the collectives staged through the host the
     # test takes the 15K shape (same code path: strong scaling, per-step partition exchange from one C call per epoch)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--repeats", "3", "--shape", "EN-FR-15K-V1"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--repeats", "3", "--shape", "EN-FR-15K-V1",
+            "--full"]
     if launcher == "self":
         cmd = [sys.executable] + tail
     else:

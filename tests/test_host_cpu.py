@@ -422,6 +422,39 @@ def test_bench_line_is_compact_strict_json():
     full["extra"]["gnn"] = {"error": "e" * 9000}
     line2 = bench.compact_line(full, None)
     assert len(line2.encode()) <= bench.COMPACT_LIMIT and json.loads(line2)["roofline"]["frac"] == r["frac"]
+    # a plain run (no --full) has no kernel-timing regions and no side legs: the contract's keys, null blocks
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "repeats", "ms_per_step",
+                                  "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+    plain.update(roofline=None, roofline_eval=None, cpu_baseline=None, extra={"ms_per_step_min": 0.07})
+    j3 = json.loads(bench.compact_line(plain, "bench_detail.json"), parse_constant=no_constants)
+    assert j3["roofline"] is None and j3["cpu_baseline"] is None and "roofline_eval" not in j3
+    assert j3["value"] == full["value"] and j3["ms_per_step"] == full["ms_per_step"] and j3["dtype"] == "f32"
+
+
+def test_bench_plain_and_full_options(monkeypatch, tmp_path):
+    """a plain `bench.py --steps K` times ONE region of K steps; --full keeps the 50 regions of the full measurement; an explicit
+    --repeats holds in both.  --dump-outputs writes float32 / float64 .npy files and refuses more than 64 MB."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def args(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.resolve_defaults(bench.parse(), 1)
+    a = args("--gpus", "1", "--steps", "300", "--warmup", "7")
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (300, 7, 1, False, None)
+    assert (a.shape, a.dim, a.batch) == ("EN-FR-100K-V1", 100, 20000)
+    a = args("--steps", "20", "--full", "--dump-outputs", str(tmp_path / "o"))
+    assert (a.repeats, a.full, a.dump_outputs) == (50, True, str(tmp_path / "o"))
+    assert args("--repeats", "3").repeats == 3 and args("--repeats", "3", "--full").repeats == 3
+    out = {"ent_embeds": np.ones((4, 3), np.float32), "loss_sum": np.array([2.5])}
+    bench.write_outputs(str(tmp_path / "o"), out)
+    for k, v in out.items():
+        got = np.load(str(tmp_path / "o" / (k + ".npy")))
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    with pytest.raises(SystemExit, match="limit"):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not os.path.exists(str(tmp_path / "big"))
 
 
 def test_refresh_shards_only_where_it_pays(monkeypatch):
