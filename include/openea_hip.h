@@ -264,6 +264,21 @@ int oea_mapping_epoch(float *ent, float *ent_acc, int64_t n_ent, float *rel, flo
                       int32_t ld, int32_t ent_l2_norm, const int32_t *batches, int32_t steps, int64_t n, float *M, float *M_acc,
                       float alpha, float lr, int32_t opt_kind, const oea_step_cfg *cfg, void *workspace, float *work,
                       double *mapping_loss_accum, double *step_loss_accum, void *stream);
+/* TransR's step (models/trans/transr.py:13-50): x = l2n(ent)[e], y' = l2n(M_r x) with M_r = rel_matrix[r] as a row-major
+ * dim x dim matrix, for h and t of the positive and of the negative (each with its own triple's relation), r = l2n(rel)[r]
+ * unprojected, loss = sum relu(margin + |h'+r-t'|^2 - |nh'+nr-nt'|^2) over the pairs (pos i, neg i).  The projections run
+ * grouped by relation on the fp32 matrix cores (M_r staged once per tile of <= 64 items).  rel_matrix [n_rel, dim*dim] (and
+ * rel_matrix_acc: Adagrad, initial 0.1) is updated inside the call, relations absent from the batch untouched and the tiles of a
+ * relation summed in a fixed order; the entity / relation row gradients go into the step workspace's scratch and the call ends
+ * with oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY).  cfg: score_kind OEA_SCORE_TRANSE, loss_kind OEA_LOSS_MARGIN,
+ * l1 = 0, opt_kind SGD or Adagrad; n_neg == n_pos; dim <= 128 (OEA_EUNSUPPORTED above).  step_workspace: as for
+ * oea_triple_step; transr_workspace: oea_transr_workspace_bytes(n_ent, n_rel, dim, max_pos) bytes for n_pos <= max_pos (no
+ * initialisation needed).  loss_accum += the batch loss. */
+size_t oea_transr_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t dim, int64_t max_pos);
+int oea_transr_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, float *rel_matrix,
+                    float *rel_matrix_acc, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg,
+                    int64_t n_neg, const oea_step_cfg *cfg, void *step_workspace, void *transr_workspace, double *loss_accum,
+                    void *stream);
 /* addresses of the entity gradient scratch and its touched flags inside a step workspace */
 int oea_step_entity_scratch(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, void **ent_grad,
                             void **ent_touched);

@@ -230,6 +230,25 @@ def mapping_epoch(ent, ent_acc, rel, rel_acc, dim, ent_l2_norm, batches, mapping
     return work
 
 
+# ---- TransR ----------------------------------------------------------------------------------------------------
+TRANSR_MAX_DIM = 128
+
+
+def transr_workspace(n_ent, n_rel, dim, max_pos, dev=None):
+    """scratch of oea_transr_step for batches of at most max_pos pairs (no initialisation needed)"""
+    return torch.empty(lib().oea_transr_workspace_bytes(n_ent, n_rel, dim, max_pos), dtype=torch.uint8, device=dev or device())
+
+
+def transr_step(ent, ent_acc, rel, rel_acc, rel_matrix, rel_matrix_acc, dim, pos, neg, cfg, workspace, transr_ws, loss_accum):
+    """One TransR optimiser step in place (oea_transr_step): rel_matrix device fp32 [R, dim*dim] (+ its Adagrad accumulator),
+    ent / rel as for triple_step, pos / neg int32 [n, 3] paired row by row; the batch loss is added to `loss_accum`."""
+    assert rel_matrix.shape == (rel.shape[0], dim * dim) and rel_matrix.dtype == torch.float32
+    n_neg = 0 if neg is None else neg.shape[0]
+    check(lib().oea_transr_step(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], _p(rel_matrix),
+                                _p(rel_matrix_acc), dim, ent.shape[1], _p(pos), pos.shape[0], _p(neg), n_neg, C.byref(cfg),
+                                _p(workspace), _p(transr_ws), _p(loss_accum), _stream()))
+
+
 def part_rows_per_rank(n_ent, world):
     return int(lib().oea_part_rows_per_rank(int(n_ent), int(world)))
 

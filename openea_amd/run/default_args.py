@@ -33,11 +33,11 @@ _ARGS = {
                           batch_size=5000, min_iter=40, neg_sampling="uniform", neg_triple_num=10, truncated_epsilon=0.9,
                           truncated_freq=10, batch_threads_num=4, start_valid=10, start_bp=5000, eval_metric="inner",
                           eval_norm=True, sim_th=0.75, k=10, sub_epoch=10, align_times=1),
-    # run/args/trans{h,d}_args_*.json (TransE takes the same set: models/trans/transe.py:20-29 asserts it)
+    # run/args/trans{h,d,r}_args_*.json (TransE takes the same set: models/trans/transe.py:20-29 asserts it)
     **{name: dict(embedding_module=name, alignment_module="sharing", dim=100, init="normal", ent_l2_norm=True,
                   rel_l2_norm=True, loss="margin-based", loss_norm="L2", margin=1.5, neg_sampling="uniform",
                   neg_triple_num=1, learning_rate=0.01, optimizer="Adagrad", batch_size=5000, eval_metric="inner",
-                  eval_norm=False) for name in ("TransE", "TransH", "TransD")},
+                  eval_norm=False) for name in ("TransE", "TransH", "TransD", "TransR")},
     "GCN_Align": dict(embedding_module="GCN_Align", alignment_module="mapping", dim=100, neg_sampling="uniform",
                       neg_triple_num=5, learning_rate=8, batch_size=5000, test_threads_num=3, eval_metric="manhattan",
                       eval_norm=False, support_number=1, se_dim=100, ae_dim=100, hidden1=100, gamma=3,
