@@ -537,7 +537,7 @@ int oea_topk_rows(const float *s, int64_t n_rows, int64_t nc, int64_t ld, int32_
  * Inner-product tiles (this call, oea_sim_matrix, oea_topk_inner): both operands are first copied into two
  * process-wide, grow-only scratch buffers in the packed layout the LDS-DMA staging reads ([n_pad, Kp], see
  * DESIGN.md "Packed similarity operands"); reuse is ordered by `stream` (a call on another stream waits for
- * the previous use).  OEA_TILE_GLDS=0 in the environment selects the register-staged tiles (same bits, no scratch).
+ * the previous use).
  * ------------------------------------------------------------------------------------- */
 enum { OEA_METRIC_INNER = 0, OEA_METRIC_MANHATTAN = 1, OEA_METRIC_EUCLIDEAN = 2,
        OEA_METRIC_MANHATTAN_F32 = 3 /* oea_sim_matrix only: 1 - sum |a - b| accumulated in fp32 -- a ranking pre-filter, not scipy's bits */ };

@@ -275,11 +275,6 @@ COMM_ALLREDUCE, COMM_ALLGATHER, COMM_REDUCE_SCATTER = 0, 1, 2
 COMM_F32, COMM_F64, COMM_I64 = 0, 1, 2
 COMM_PHASES = ("grad", "pack", "reduce_scatter", "apply", "all_gather", "unpack")
 
-def tile_glds():
-    """the packed (LDS-DMA) tile path is on unless OEA_TILE_GLDS=0 (csrc/sim_rank.hip)"""
-    return os.environ.get("OEA_TILE_GLDS", "1")[:1] != "0"
-
-
 _lib = None
 
 

@@ -38,7 +38,6 @@ bool prof_pair(hipEvent_t *start, hipEvent_t *stop);
     } while (0)
 
 // packed-operand path of the similarity tiles (sim_rank.hip), for the kNN strips of topk.hip
-bool tile_glds_enabled();
 int pack_rows(int slot, const float *src, int64_t n, int ld, int dim, hipStream_t st, float **packed, int *kp);
 int release_packed_rows(hipStream_t st);
 void sim_inner_store_packed(const float *e1p, int64_t n1, const float *e2p, int64_t n2, int kp, int dim, float *out,

@@ -10,11 +10,11 @@
 //                                      written (19.6 GB at 70,000^2 in the reference)
 //   scipy cdist('cityblock')         -> fp64 VALU tiles, sequential k (bit-exact vs scipy)
 //
-// Operand layout: both operands are row-major [n, ld] fp32 (K contiguous).  A K-chunk of 32
-// is staged global -> registers -> LDS with the k index permuted inside groups of 8
-// (positions 0..3 hold k = 0,2,4,6; 4..7 hold k = 1,3,5,7) so that one ds_read_b128 gives a
-// lane its operand for four consecutive MFMA k-steps in natural k order.  Row stride 36
-// floats (144 B) makes the b128 reads bank-conflict free.
+// Operand layout: the callers' tables are row-major [n, ld] fp32 (K contiguous).  Each call first
+// packs both operands ([n_pad, Kp], the k index permuted inside groups of 8: positions 0..3 hold
+// k = 0,2,4,6, 4..7 hold k = 1,3,5,7) so that one ds_read_b128 gives a lane its operand for four
+// consecutive MFMA k-steps in natural k order; K-chunks of 32 then go HBM/L2 -> LDS by LDS-DMA
+// (see "packed operands + LDS-DMA staging" below).
 #include "common.h"
 #include <stdlib.h>
 #include <cmath>
@@ -25,7 +25,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TILE = 128;      // block tile edge (both operands)
 constexpr int BK = 32;         // K chunk
-constexpr int LDS_LD = BK + 4; // padded row stride (floats)
+constexpr int LDS_LD = BK + 4; // floats per row of an LDS chunk buffer (a packed chunk fills BK of them)
 
 // ---- XCD-aware order of the (query tile, candidate chunk) work items (round 5) --------------------------------------------------
 // Block b of a launch runs on XCD b % 8 (observed dispatch rule, MI355X_MICROARCH.md: "for speed only"), and every XCD has its own
@@ -51,75 +51,6 @@ __device__ __forceinline__ uint32_t f2ord(float f) {   // order-preserving float
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// A K-chunk of one 128-row operand tile in flight between HBM/L2 and LDS: 4 float4 per thread.
-struct Frag { float4 v[4]; };
-
-// rows [row0, row0+128) x k [k0, k0+32) of `src` -> registers.  Rows past the matrix are clamped to
-// its last row (their products are discarded by the epilogues), so that interior chunks are four
-// plain 16-byte loads from a tile base + 32-bit offsets; only the chunk that crosses `dim` masks.
-__device__ __forceinline__ void load_frag(const float *__restrict__ src, int64_t n, int ld, int dim, int64_t row0,
-                                          int k0, int tid, Frag &f) {
-    const float *base = src + row0 * ld;                                  // wave-uniform
-    const int last = (int)(n - 1 - row0 < TILE - 1 ? n - 1 - row0 : TILE - 1);
-    const int c = k0 + (tid & 7) * 4;
-    if (k0 + BK <= dim) {
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int r = min((tid >> 3) + pass * 32, last);
-            f.v[pass] = oea::ld4(base + r * ld + c);
-        }
-    } else {
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int r = min((tid >> 3) + pass * 32, last);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < ld) {
-                v = oea::ld4(base + r * ld + c);
-                if (c + 0 >= dim) v.x = 0.f;
-                if (c + 1 >= dim) v.y = 0.f;
-                if (c + 2 >= dim) v.z = 0.f;
-                if (c + 3 >= dim) v.w = 0.f;
-            }
-            f.v[pass] = v;
-        }
-    }
-}
-
-// registers -> LDS with the k permutation described above
-__device__ __forceinline__ void store_frag(const Frag &f, float *__restrict__ dst, int tid) {
-    const int q = tid & 7, g = q >> 1, half = q & 1;
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        float *p = dst + ((tid >> 3) + pass * 32) * LDS_LD + g * 8;
-        *reinterpret_cast<float2 *>(p + 2 * half) = make_float2(f.v[pass].x, f.v[pass].z);
-        *reinterpret_cast<float2 *>(p + 4 + 2 * half) = make_float2(f.v[pass].y, f.v[pass].w);
-    }
-}
-
-// acc += A-chunk (M rows) x B-chunk (N rows) over `groups` groups of 8 k; per wave a 64x64 sub-tile
-__device__ __forceinline__ void mma_chunk(const float *__restrict__ As, const float *__restrict__ Bs, int groups,
-                                          f32x16 (&acc)[2][2]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const float *ap = As + (wm * 64 + (lane & 31)) * LDS_LD + 4 * (lane >> 5);
-    const float *bp = Bs + (wn * 64 + (lane & 31)) * LDS_LD + 4 * (lane >> 5);
-    for (int g = 0; g < groups; ++g) {
-        const float4 a0 = *reinterpret_cast<const float4 *>(ap + g * 8);
-        const float4 a1 = *reinterpret_cast<const float4 *>(ap + 32 * LDS_LD + g * 8);
-        const float4 b0 = *reinterpret_cast<const float4 *>(bp + g * 8);
-        const float4 b1 = *reinterpret_cast<const float4 *>(bp + 32 * LDS_LD + g * 8);
-        const float av[2][4] = {{a0.x, a0.y, a0.z, a0.w}, {a1.x, a1.y, a1.z, a1.w}};
-        const float bv[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[0][s], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[1][s], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[0][s], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[1][s], acc[1][1], 0, 0, 0);
-        }
-    }
-}
-
 __device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -129,72 +60,17 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 }
 
-// Software pipeline over a sequence of `n_tiles` M-tiles against one fixed N-tile: chunk i+1 travels
-// HBM/L2 -> registers while chunk i is on the matrix cores, and lands in the other LDS buffer
-// (one barrier per chunk).  `epilogue(t, acc)` runs after the last chunk of M-tile t with the
-// first chunk of tile t+1 already in flight.  LDS: As/Bs = 2 buffers of TILE*LDS_LD floats each.
-template <class MTile, class Epilogue>
-__device__ __forceinline__ void tile_pipeline(const float *__restrict__ am, int64_t m_rows, int lda,
-                                              const float *__restrict__ bn, int64_t n_rows, int ldb, int dim,
-                                              int64_t n0, int64_t n_tiles, MTile m_tile, float *As, float *Bs,
-                                              Epilogue epilogue) {
-    const int tid = threadIdx.x;
-    const int kend = (dim + 7) / 8 * 8;
-    const int nchunk = (kend + BK - 1) / BK;
-    const int64_t total = n_tiles * nchunk;
-    if (total == 0) return;
-    constexpr int BUF = TILE * LDS_LD;
-    Frag fa, fb;
-    load_frag(am, m_rows, lda, dim, m_tile(0), 0, tid, fa);
-    load_frag(bn, n_rows, ldb, dim, n0, 0, tid, fb);
-    store_frag(fa, As, tid);
-    store_frag(fb, Bs, tid);
-    __syncthreads();
-    if (total > 1) {
-        const int64_t t1 = 1 / nchunk;
-        const int k1 = (1 % nchunk) * BK;
-        load_frag(am, m_rows, lda, dim, m_tile(t1), k1, tid, fa);
-        load_frag(bn, n_rows, ldb, dim, n0, k1, tid, fb);
-    }
-    f32x16 acc[2][2];
-    zero_acc(acc);
-    int64_t t = 0;
-    int kc = 0;
-    for (int64_t it = 0; it < total; ++it) {
-        const int cur = (int)(it & 1);
-        mma_chunk(As + cur * BUF, Bs + cur * BUF, min(BK, kend - kc * BK) / 8, acc);
-        if (it + 1 < total) {
-            store_frag(fa, As + (cur ^ 1) * BUF, tid);
-            store_frag(fb, Bs + (cur ^ 1) * BUF, tid);
-        }
-        __syncthreads();
-        if (it + 2 < total) {
-            int kc2 = kc + 2;
-            int64_t t2 = t;
-            while (kc2 >= nchunk) { kc2 -= nchunk; ++t2; }
-            load_frag(am, m_rows, lda, dim, m_tile(t2), kc2 * BK, tid, fa);
-            load_frag(bn, n_rows, ldb, dim, n0, kc2 * BK, tid, fb);
-        }
-        if (++kc == nchunk) {
-            epilogue(t, acc);
-            zero_acc(acc);
-            kc = 0;
-            ++t;
-        }
-    }
-}
-
 // ---- packed operands + LDS-DMA staging --------------------------------------------------------------------------
-// The same pipeline fed by `global_load_lds_dwordx4` (gfx950): a chunk goes HBM/L2 -> LDS without passing through
-// registers and without ds_write instructions.  The LDS-DMA destination of one wave instruction is lane-linear
-// (base + 16 B * lane), so the k permutation of the reg-staged path cannot be applied on the way: the operands are
-// packed once per call by pack_rows_kernel ([n_pad, Kp] with n_pad % 128 == 0 and Kp % 32 == 0, zero filled, every
-// group of 8 k stored as k = 0,2,4,6,1,3,5,7 -- O(n d) work in front of an O(n^2 d) sweep).  The LDS image of a chunk
-// is 128 rows x 32 floats WITHOUT padding; bank conflicts are avoided by an XOR swizzle of the eight 16-byte columns
-// of a row with ((row >> 1) & 7), applied to the per-lane SOURCE address of the DMA and to the ds_read address (the same
-// involution on both sides).  A 128-byte row covers half of the 64 banks, so 16 consecutive rows of one column must
-// land on all 16 (row parity, position) combinations: with (row & 7) rows r and r + 8 collided -- SQ_LDS_BANK_CONFLICT
-// was half of SQ_LDS_IDX_ACTIVE -- with ((row >> 1) & 7) they do not.
+// A chunk goes HBM/L2 -> LDS by `global_load_lds_dwordx4` (gfx950) without passing through registers and without
+// ds_write instructions.  The LDS-DMA destination of one wave instruction is lane-linear (base + 16 B * lane), so the k
+// permutation cannot be applied on the way: the operands are packed once per call by pack_rows_kernel ([n_pad, Kp] with
+// n_pad % 128 == 0 and Kp % 32 == 0, zero filled, every group of 8 k stored as k = 0,2,4,6,1,3,5,7 -- O(n d) work in
+// front of an O(n^2 d) sweep).  The LDS image of a chunk is 128 rows x 32 floats WITHOUT padding; bank conflicts are
+// avoided by an XOR swizzle of the eight 16-byte columns of a row with ((row >> 1) & 7), applied to the per-lane SOURCE
+// address of the DMA and to the ds_read address (the same involution on both sides).  A 128-byte row covers half of the
+// 64 banks, so 16 consecutive rows of one column must land on all 16 (row parity, position) combinations: with
+// (row & 7) rows r and r + 8 collided -- SQ_LDS_BANK_CONFLICT was half of SQ_LDS_IDX_ACTIVE -- with ((row >> 1) & 7)
+// they do not.
 constexpr int PLD = BK;                 // unpadded LDS row stride (floats)
 
 __global__ void pack_rows_kernel(const float *__restrict__ src, int64_t n, int ld, int dim, float *__restrict__ dst,
@@ -258,9 +134,12 @@ __device__ __forceinline__ void mma_chunk_packed(const float *__restrict__ As, c
     }
 }
 
-// tile_pipeline on packed operands (am / bn: packed arrays, lda = ldb = Kp; rows are padded, so no clamping): the DMA of
-// chunk i+1 is issued into the other LDS buffer before chunk i goes to the matrix cores; the barrier at the end of the
-// iteration (with the vmcnt(0) the compiler puts in front of it) makes it visible and frees the buffer just read.
+// Software pipeline over a sequence of `n_tiles` M-tiles against one fixed N-tile on packed operands (am / bn: packed
+// arrays, Kp floats per row; rows are padded, so no clamping): the DMA of chunk i+1 is issued into the other LDS buffer
+// before chunk i goes to the matrix cores; the barrier at the end of the iteration (with the vmcnt(0) the compiler puts in
+// front of it) makes it visible and frees the buffer just read.  `epilogue(t, acc)` runs after the last chunk of M-tile t.
+// LDS: As/Bs = 2 buffers of TILE*LDS_LD floats each.  The fp32 tile kernels receive the packed operands and their Kp in the
+// (table, ld) arguments.
 template <class MTile, class Epilogue>
 __device__ __forceinline__ void tile_pipeline_packed(const float *__restrict__ am, int kp, const float *__restrict__ bn,
                                                      int dim, int64_t n0, int64_t n_tiles, MTile m_tile, float *As,
@@ -269,7 +148,7 @@ __device__ __forceinline__ void tile_pipeline_packed(const float *__restrict__ a
     const int nchunk = (kend + BK - 1) / BK;
     const int64_t total = n_tiles * nchunk;
     if (total == 0) return;
-    constexpr int BUF = TILE * LDS_LD;                                // the buffers keep the reg-staged path's size
+    constexpr int BUF = TILE * LDS_LD;
     stage_packed(am, kp, m_tile(0), 0, As);
     stage_packed(bn, kp, n0, 0, Bs);
     __syncthreads();
@@ -522,12 +401,12 @@ __device__ __forceinline__ void mma_bf_frag(const BfFrag &f, f32x16 (&acc)[2][2]
     acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a1l, f.b1h, acc[1][1], 0, 0, 0);
 }
 
-// PF (OEA_BF16_BIG_MODE=1, the default; 0 = !PF): the fragment reads never wait in front of idle matrix cores.  A chunk is two k-steps; the loop
+// PF (the plain sweeps): the fragment reads never wait in front of idle matrix cores.  A chunk is two k-steps; the loop
 // body is  [reads of k-step 1 of chunk c] [MFMAs of k-step 0] [chunk c + 1 landed? counted vmcnt, raw barrier] [DMA of chunk c + 3 into
 // the slot chunk c just left] [reads of k-step 0 of chunk c + 1] [MFMAs of k-step 1 of chunk c]: every read is issued one MFMA group
 // (12 x 32 cycles) before its use, the barrier sits between the two groups, and the DMA runs three chunks ahead.  The second k-step of
 // a tile's last chunk may be zero padding of the packed rows (Kp is a multiple of 32): it adds +0.  !PF = the first form of this
-// pipeline (reads in front of each group, barrier at the top), kept for the ablation.
+// pipeline (reads in front of each group, barrier at the top): the sweep with the CSLS terms in its epilogue, where PF spills.
 template <bool PF, class MTile, class Epilogue>
 __device__ __forceinline__ void tile_pipeline_bf16_big(const float *__restrict__ am, int kp, const float *__restrict__ bn, int dim,
                                                        int64_t n0, int64_t n_tiles, MTile m_tile, float *lds, Epilogue epilogue) {
@@ -609,114 +488,6 @@ __device__ __forceinline__ void tile_pipeline_bf16_big(const float *__restrict__
             if (it + 3 < total) issue();                                     // into the slot of chunk it
             const float *nxt = lds + sc * BIG_STAGE;
             load_bf_frag(nxt + a_off, nxt + b_off, 0, half, x, f0);          // k-step 0 of the next chunk, behind the MFMAs of k-step 1
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mma_bf_frag(f1, acc);
-        __builtin_amdgcn_sched_barrier(0);
-        ++kc;
-        if ((kc & (kBf16BlockChunks - 1)) == 0 || kc == nchunk) {
-            add_acc(tot, acc);
-            zero_acc(acc);
-        }
-        if (kc == nchunk) {
-            epilogue((int64_t)t, tot);
-            zero_acc(tot);
-            kc = 0;
-            ++t;
-        }
-    }
-}
-
-// ---- producer / consumer waves (round 5, OEA_BF16_BIG_MODE=2; not the default: measured equal to mode 1) -------------------------
-// Hypothesis: what the 256 x 128 pipeline above spends its time on is the ISSUE of its LDS-DMA: a `global_load_lds_dwordx4` costs the
-// issuing wave ~60-180 cycles when it sits between MFMAs and fragment reads (MI355X_MICROARCH.md), 6 per wave and chunk = a third
-// of an iteration on every SIMD; a wave that does nothing else issues one in ~25 cycles.  So of the 8 waves of the workgroup (two per
-// SIMD, 256 VGPRs each: more waves would halve the register budget of the multiplying ones) waves 6 and 7 become LOADERS -- each
-// issues half of a stage's 40 instructions, waits for the stage the consumers need next (counted vmcnt) and meets them at the
-// barrier -- and waves 0-5 are CONSUMERS as 3 (M) x 2 (N) on 192 candidate rows x 128 query rows: fragment reads one MFMA group
-// ahead, MFMAs, K-block sums, epilogue, and nothing else.  LDS: 3 stages x (192 + 128) x 128 B = 120 KB.
-// Measured at 70,000^2 x 1,200: 35.3 ms against 34.7 ms for mode 1 -- six multiplying waves each run 1.3x faster than eight did, which
-// cancels; identical results.  (hipcc still answers the loop-carried fragment reads with lgkmcnt(0) in front of the first MFMA
-// group and counted waits on the NEXT chunk's reads in the second: the prefetch of both modes is only half effective.)
-constexpr int SPEC_MT = 192, SPEC_NC = 6;
-constexpr int SPEC_A = SPEC_MT * PLD;
-constexpr int SPEC_STAGE = SPEC_A + TILE * PLD;            // 40 KB
-constexpr int SPEC_BLOCKS = (SPEC_MT + TILE) / 8;          // 8-row pieces of a stage: 24 of A, 16 of B
-
-template <class MTile, class Epilogue>
-__device__ __forceinline__ void tile_pipeline_bf16_spec(const float *__restrict__ am, int kp, const float *__restrict__ bn, int dim,
-                                                        int64_t n0, int64_t n_tiles, MTile m_tile, float *lds, Epilogue epilogue) {
-    const int S = (dim + 15) / 16;
-    const int nchunk = (S + 1) / 2;
-    const int total = (int)n_tiles * nchunk;
-    if (total <= 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (wave >= SPEC_NC) {
-        // ---- loader ------------------------------------------------------------------------------------------------------------
-        const int lw = wave - SPEC_NC, sub = lane >> 3;
-        const unsigned c_even = 4u * ((lane & 7) ^ ((sub >> 1) & 7)), c_odd = 4u * ((lane & 7) ^ ((4 + (sub >> 1)) & 7));
-        const float *b_base = bn + n0 * kp;
-        int ti = 0, ki = 0, si = 0;
-        const float *a_base = am + m_tile(0) * kp;
-        auto issue = [&]() {
-            float *slot = lds + si * SPEC_STAGE;
-            const float *a_tile = a_base + ki * BK, *b_tile = b_base + ki * BK;
-#pragma unroll
-            for (int u = 0; u < SPEC_BLOCKS / 2; ++u) {
-                const int b = lw * (SPEC_BLOCKS / 2) + u;                    // loader 0: A pieces 0-19; loader 1: A 20-23, B 0-15
-                const bool is_a = b < SPEC_MT / 8;
-                const int piece = is_a ? b : b - SPEC_MT / 8;
-                const float *src = (is_a ? a_tile : b_tile) + (size_t)((unsigned)(piece * 8 + sub) * (unsigned)kp + (piece & 1 ? c_odd : c_even));
-                float *base = slot + (is_a ? 0 : SPEC_A) + piece * 8 * PLD;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                 reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(base)),
-                                                 16, 0, 0);
-            }
-            si = si == BIG_STAGES - 1 ? 0 : si + 1;
-            if (++ki == nchunk) { ki = 0; ++ti; a_base = am + m_tile(ti) * kp; }
-        };
-        issue();
-        if (total > 1) issue();
-        if (total > 2) issue();
-        if (total > 2) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-        else if (total > 1) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        for (int it = 0; it + 1 < total; ++it) {
-            // chunk it + 1 landed (of this wave's DMA only chunk it + 2's 20 instructions may still be out)
-            if (it + 2 < total) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (it + 3 < total) issue();                                     // into the slot the consumers have just left
-        }
-        return;
-    }
-    // ---- consumer ----------------------------------------------------------------------------------------------------------------
-    const int wm = wave >> 1, wn = wave & 1;
-    const int x = (lane >> 1) & 7, half = lane >> 5;
-    const int a_off = (wm * 64 + (lane & 31)) * PLD, b_off = SPEC_A + (wn * 64 + (lane & 31)) * PLD;
-    f32x16 acc[2][2], tot[2][2];
-    zero_acc(acc);
-    zero_acc(tot);
-    int t = 0, kc = 0, sc = 0;
-    __builtin_amdgcn_s_barrier();                                            // chunk 0 landed
-    asm volatile("" ::: "memory");
-    BfFrag f0, f1;
-    load_bf_frag(lds + a_off, lds + b_off, 0, half, x, f0);
-    for (int it = 0; it < total; ++it) {
-        const float *slot = lds + sc * SPEC_STAGE;
-        load_bf_frag(slot + a_off, slot + b_off, 1, half, x, f1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_bf_frag(f0, acc);
-        __builtin_amdgcn_sched_barrier(0);
-        sc = sc == BIG_STAGES - 1 ? 0 : sc + 1;
-        if (it + 1 < total) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // f1 is here: nobody reads chunk it's slot after the barrier
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const float *nxt = lds + sc * SPEC_STAGE;
-            load_bf_frag(nxt + a_off, nxt + b_off, 0, half, x, f0);
         }
         __builtin_amdgcn_sched_barrier(0);
         mma_bf_frag(f1, acc);
@@ -837,15 +608,6 @@ __device__ __forceinline__ void tile_pipeline_bf16_breg(const float *__restrict_
         }
         __syncthreads();
     }
-}
-
-// one call site for both stagings: PACKED kernels receive packed operands and their Kp in the ld arguments
-template <bool PACKED, class MTile, class Epilogue>
-__device__ __forceinline__ void run_tiles(const float *__restrict__ am, int64_t m_rows, int lda, const float *__restrict__ bn,
-                                          int64_t n_rows, int ldb, int dim, int64_t n0, int64_t n_tiles, MTile m_tile,
-                                          float *As, float *Bs, Epilogue epilogue) {
-    if constexpr (PACKED) tile_pipeline_packed(am, lda, bn, dim, n0, n_tiles, m_tile, As, Bs, epilogue);
-    else tile_pipeline(am, m_rows, lda, bn, n_rows, ldb, dim, n0, n_tiles, m_tile, As, Bs, epilogue);
 }
 
 // ---- gold similarity: S_ii as the same k-ordered fmaf chain (one lane per query) ---------------
@@ -1019,7 +781,7 @@ __global__ __launch_bounds__(256) void eval_prologue_kernel(const float *__restr
 // grid.x = query tiles, grid.y = candidate chunks.  Per lane: one query (MFMA column) and 16
 // candidates per MFMA tile, so the per-query reductions stay in registers across the whole
 // candidate sweep; partial results are merged with integer atomics (order independent).
-template <bool CSLS, bool PACKED>
+template <bool CSLS>
 __global__ __launch_bounds__(256, 2) void rank_inner_kernel(
     const float *__restrict__ e1, int64_t n1, int ld1, const float *__restrict__ e2, int64_t n2, int ld2,
     int dim, const float *__restrict__ gold, const float *__restrict__ csls_r, const float *__restrict__ csls_c,
@@ -1046,8 +808,8 @@ __global__ __launch_bounds__(256, 2) void rank_inner_kernel(
         g[tn] = ok ? gold[qi[tn]] : 0.f;
         rq[tn] = (ok && CSLS) ? csls_r[qi[tn]] : 0.f;
     }
-    run_tiles<PACKED>(
-        e2, n2, ld2, e1, n1, ld1, dim, q0, ct_end > ct_begin ? ct_end - ct_begin : 0,
+    tile_pipeline_packed(
+        e2, ld2, e1, dim, q0, ct_end > ct_begin ? ct_end - ct_begin : 0,
         [=](int64_t t) { return (ct_begin + t) * TILE; }, As, Bs,
         [&](int64_t t, f32x16 (&acc)[2][2]) {
             const int64_t c0 = (ct_begin + t) * TILE;
@@ -1125,7 +887,7 @@ __global__ __launch_bounds__(256, 2) void rank_inner_kernel(
 // every pair with v~ >= thr - tol (tol = *tol_ptr bounds |v~ - v|): list_select_kernel decides the neighbourhood of the k-th value
 // with exact chains -- the same sets as the fp32 sweep
 // NCH > 0 (BF16 only): the query operand in registers (tile_pipeline_bf16_breg, Kp = 32 NCH)
-template <bool PACKED, bool BF16 = false, int NCH = 0>
+template <bool BF16 = false, int NCH = 0>
 __global__ __launch_bounds__(256, 2) void topk_append_kernel(
     const float *__restrict__ q, int64_t nq, int ldq, const float *__restrict__ c, int64_t nc, int ldc, int dim,
     const float *__restrict__ thr, int tiles_per_chunk, int cap, float *__restrict__ list_vals, int32_t *__restrict__ list_cols,
@@ -1190,7 +952,7 @@ __global__ __launch_bounds__(256, 2) void topk_append_kernel(
     auto m_tile = [=](int64_t t) { return (ct_begin + t) * TILE; };
     if constexpr (BF16 && NCH > 0) tile_pipeline_bf16_breg<NCH>(c, ldc, q, q0, n_tiles, m_tile, As, epilogue, dim);
     else if constexpr (BF16) tile_pipeline_bf16<false>(c, ldc, q, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
-    else run_tiles<PACKED>(c, nc, ldc, q, nq, ldq, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
+    else tile_pipeline_packed(c, ldc, q, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn)
         if (qi[tn] < nq) counts[qi[tn] * nseg + sidx] = (int32_t)((boff[tn] - bbeg[tn]) >> 2);
@@ -1209,7 +971,7 @@ __global__ __launch_bounds__(256, 2) void topk_append_kernel(
 // BF16: e = the hi / lo split rows (pack_rows_bf16_kernel), the values appended are v~ with |v~ - v| <= *tol_ptr, and the cut is
 // thr - tol: every pair whose EXACT value reaches thr is in the lists (the select resolves the neighbourhood of the k-th
 // value with exact chains, list_select_kernel).
-template <bool PACKED, bool BF16>
+template <bool BF16>
 __global__ __launch_bounds__(256, 2) void topk_append_sym_kernel(
     const float *__restrict__ e, int64_t n, int ld, int dim, const float *__restrict__ thr, const int4 *__restrict__ items,
     int nseg, int cap, float *__restrict__ list_vals, int32_t *__restrict__ list_cols, int32_t *__restrict__ counts, int T, int ccap,
@@ -1292,7 +1054,7 @@ __global__ __launch_bounds__(256, 2) void topk_append_sym_kernel(
         };
     auto m_tile = [=](int64_t t) { return (int64_t)(item.y + t) * TILE; };
     if constexpr (BF16) tile_pipeline_bf16<false>(e, ld, e, dim, q0, (int64_t)(item.z - item.y), m_tile, As, Bs, epilogue);
-    else run_tiles<PACKED>(e, n, ld, e, n, ld, dim, q0, (int64_t)(item.z - item.y), m_tile, As, Bs, epilogue);
+    else tile_pipeline_packed(e, ld, e, dim, q0, (int64_t)(item.z - item.y), m_tile, As, Bs, epilogue);
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn)
         if (qi[tn] < n) counts[qi[tn] * nseg + sidx] = (int32_t)((boff[tn] - bbeg[tn]) >> 2);
@@ -1634,7 +1396,6 @@ __global__ void rank_finalize_kernel(const unsigned long long *__restrict__ best
 }
 
 // ---- store epilogue: M = e1 rows (output rows), N = e2 rows (output columns) ----------------------
-template <bool PACKED>
 __global__ __launch_bounds__(256, 2) void sim_inner_store_kernel(const float *__restrict__ e1, int64_t n1, int ld1,
                                                               const float *__restrict__ e2, int64_t n2, int ld2,
                                                               int dim, float *__restrict__ out, int64_t ld_out,
@@ -1645,8 +1406,8 @@ __global__ __launch_bounds__(256, 2) void sim_inner_store_kernel(const float *__
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int64_t m0 = (int64_t)blockIdx.y * TILE, c0 = (int64_t)blockIdx.x * TILE;
-    run_tiles<PACKED>(
-        e1, n1, ld1, e2, n2, ld2, dim, c0, 1, [=](int64_t) { return m0; }, As, Bs,
+    tile_pipeline_packed(
+        e1, ld1, e2, dim, c0, 1, [=](int64_t) { return m0; }, As, Bs,
         [&](int64_t, f32x16 (&acc)[2][2]) {
             float *tile = out + m0 * ld_out + c0;                                    // wave-uniform
             const int rows_left = (int)(n1 - m0 < TILE ? n1 - m0 : TILE), cols_left = (int)(n2 - c0 < TILE ? n2 - c0 : TILE);
@@ -2521,15 +2282,14 @@ static unsigned tile_grid_blocks(const TileGrid &g) { return g.per ? 8u * g.per 
 // can belong to the exact top k and recomputes them with the exact chain.
 // NW = 8 (BF16, K > 128): 512 threads on 256-candidate tiles through the three-stage ring (tile_pipeline_bf16_big, dynamic LDS);
 // the query lists then have 8 * chunks segments (one per chunk, wave row and half-wave)
-template <bool PACKED, bool BF16, int NCH = 0, int NW = 4, int MODE = 1>
+template <bool BF16, int NCH = 0, int NW = 4>
 __global__ __launch_bounds__(NW * 64, 2) void csls_append_kernel(
     const float *__restrict__ q, int64_t nq, int ldq, const float *__restrict__ c, int64_t nc, int ldc, int dim,
     const float *__restrict__ thr_q, const float *__restrict__ thr_c, int tiles_per_chunk, int cap, int ccap,
     float *__restrict__ qlists, int32_t *__restrict__ qcounts, float *__restrict__ clists, int32_t *__restrict__ ccounts,
     const float *__restrict__ tol_ptr, TileGrid tg) {
     constexpr uint32_t ES = BF16 ? 8u : 4u;                 // bytes per list entry
-    constexpr int NC = (NW == 8 && MODE == 2) ? SPEC_NC : NW;       // multiplying waves (MODE 2: waves 6 and 7 only load)
-    constexpr int MT = NC * 32;                             // candidate rows of a tile
+    constexpr int MT = NW * 32;                             // candidate rows of a tile
     extern __shared__ __attribute__((aligned(16))) float csls_dyn_lds[];          // NW == 8: BIG_LDS_BYTES
     __shared__ __attribute__((aligned(16))) float lds_static[NW == 8 ? 4 : (NCH > 0 ? 4 * TILE * PLD : 4 * TILE * LDS_LD)];
     float *lds = NW == 8 ? csls_dyn_lds : lds_static;
@@ -2547,8 +2307,8 @@ __global__ __launch_bounds__(NW * 64, 2) void csls_append_kernel(
     const int64_t nct = (nc + MT - 1) / MT;
     const int64_t ct_begin = (int64_t)by * tiles_per_chunk;
     const int64_t ct_end = (ct_begin + tiles_per_chunk < nct) ? ct_begin + tiles_per_chunk : nct;
-    const int nseg = NC * (int)tg.ny;
-    const int sidx = ((int)by * (NC / 2) + wm) * 2 + half;        // (a loader wave has no segment)
+    const int nseg = NW * (int)tg.ny;
+    const int sidx = ((int)by * (NW / 2) + wm) * 2 + half;
     float th[2];
     uint32_t boff[2], bbeg[2], blast[2];
     int64_t qi[2];
@@ -2614,13 +2374,10 @@ __global__ __launch_bounds__(NW * 64, 2) void csls_append_kernel(
         };
     auto m_tile = [=](int64_t t) { return (ct_begin + t) * MT; };
     const int64_t n_tiles = ct_end > ct_begin ? ct_end - ct_begin : 0;
-    if constexpr (BF16 && NW == 8 && MODE == 2) {
-        tile_pipeline_bf16_spec(c, ldc, q, dim, q0, n_tiles, m_tile, lds, epilogue);
-        if (wave >= NC) return;                                // a loader
-    } else if constexpr (BF16 && NW == 8) tile_pipeline_bf16_big<MODE == 1>(c, ldc, q, dim, q0, n_tiles, m_tile, lds, epilogue);
+    if constexpr (BF16 && NW == 8) tile_pipeline_bf16_big<true>(c, ldc, q, dim, q0, n_tiles, m_tile, lds, epilogue);
     else if constexpr (BF16 && NCH > 0) tile_pipeline_bf16_breg<NCH>(c, ldc, q, q0, n_tiles, m_tile, As, epilogue, dim);
     else if constexpr (BF16) tile_pipeline_bf16<true>(c, ldc, q, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
-    else run_tiles<PACKED>(c, nc, ldc, q, nq, ldq, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
+    else tile_pipeline_packed(c, ldc, q, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn)
         if (qi[tn] < nq) qcounts[qi[tn] * nseg + sidx] = (int32_t)((boff[tn] - bbeg[tn]) / ES);
@@ -2873,13 +2630,6 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float *__restrict_
 }
 
 // ---- host side of the packed path ---------------------------------------------------------------------------------
-// OEA_TILE_GLDS=0 selects the register-staged pipeline (kept for A/B measurements and as the reference of the
-// bit-exactness test between the two stagings).
-static bool use_glds() {
-    static const bool on = [] { const char *e = getenv("OEA_TILE_GLDS"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 struct PackedOp {
     float *p = nullptr;      // [n_pad, kp] in the process-wide scratch slot
     int kp = 0;
@@ -2942,7 +2692,7 @@ static int release_packed(hipStream_t st) {
 
 static void launch_store_packed(const float *e1p, int64_t n1, const float *e2p, int64_t n2, int kp, int dim, float *out,
                                 int64_t ld_out, hipStream_t st) {
-    sim_inner_store_kernel<true><<<dim3((unsigned)oea::ceil_div(n2, TILE), (unsigned)oea::ceil_div(n1, TILE)), 256, 0, st>>>(
+    sim_inner_store_kernel<<<dim3((unsigned)oea::ceil_div(n2, TILE), (unsigned)oea::ceil_div(n1, TILE)), 256, 0, st>>>(
         e1p, n1, kp, e2p, n2, kp, dim, out, ld_out, nullptr);
 }
 
@@ -3034,10 +2784,9 @@ __device__ __forceinline__ void rank_bf16_tile(Acc &acc, int jb, int n2, const f
 }
 
 // NCH = 0: both operands through LDS (tile_pipeline_bf16, any Kp); NCH = Kp / 32 in {1..4}: B in registers (tile_pipeline_bf16_breg);
-// NW = 8: 512 threads on 256-candidate tiles through the three-stage ring (tile_pipeline_bf16_big; tiles_per_chunk counts THOSE tiles)
-// MODE (NW = 8): 0 / 1 = tile_pipeline_bf16_big<PF = MODE> on 256-candidate tiles, all 8 waves multiply; 2 = tile_pipeline_bf16_spec on
-// 192-candidate tiles: waves 0-5 multiply, waves 6-7 load
-template <bool WARM, bool CSLS, int NCH, int NW = 4, int MODE = 1>
+// NW = 8: 512 threads on 256-candidate tiles through the three-stage ring (tile_pipeline_bf16_big<PF>; tiles_per_chunk counts THOSE
+// tiles)
+template <bool WARM, bool CSLS, int NCH, int NW = 4, bool PF = true>
 __device__ __forceinline__ void rank_bf16_body(
     const float *__restrict__ qp, int64_t n1, int kp, const float *__restrict__ cp, int64_t n2, int dim,
     const float *__restrict__ gold, const float *__restrict__ tol_ptr, const float *__restrict__ csls_r,
@@ -3049,8 +2798,7 @@ __device__ __forceinline__ void rank_bf16_body(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int64_t q0 = (int64_t)bx * TILE;
-    constexpr int NC = (NW == 8 && MODE == 2) ? SPEC_NC : NW;   // multiplying waves
-    constexpr int MT = NC * 32;                              // candidate rows of a tile
+    constexpr int MT = NW * 32;                              // candidate rows of a tile
     const int64_t nct = (n2 + MT - 1) / MT;
     const int64_t ct_begin = (int64_t)by * tiles_per_chunk;
     const int64_t ct_end = (ct_begin + tiles_per_chunk < nct) ? ct_begin + tiles_per_chunk : nct;
@@ -3119,13 +2867,7 @@ __device__ __forceinline__ void rank_bf16_body(
         };
     auto m_tile = [=](int64_t t) { return (ct_begin + t) * MT; };
     const int64_t n_tiles = ct_end > ct_begin ? ct_end - ct_begin : 0;
-    if constexpr (NW == 8 && MODE == 2) {
-        tile_pipeline_bf16_spec(cp, kp, qp, dim, q0, n_tiles, m_tile, As, epilogue);
-        if (wave >= NC) {                                  // a loader: no ranks, an empty record slice
-            if (!WARM && lane == 0) rec_cnt[2 + wid] = 0u;
-            return;
-        }
-    } else if constexpr (NW == 8) tile_pipeline_bf16_big<MODE == 1>(cp, kp, qp, dim, q0, n_tiles, m_tile, As, epilogue);
+    if constexpr (NW == 8) tile_pipeline_bf16_big<PF>(cp, kp, qp, dim, q0, n_tiles, m_tile, As, epilogue);
     else if constexpr (NCH > 0) tile_pipeline_bf16_breg<NCH>(cp, kp, qp, q0, n_tiles, m_tile, As, epilogue, dim);
     else tile_pipeline_bf16<true>(cp, kp, qp, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
 #pragma unroll
@@ -3165,10 +2907,10 @@ __global__ __launch_bounds__(256, 2) void rank_bf16_breg_kernel(OEA_RANK_BF16_PA
     rank_bf16_body<WARM, CSLS, NCH>(OEA_RANK_BF16_ARGS, As, nullptr);
 }
 
-template <bool CSLS, int MODE>
+template <bool CSLS, bool PF>
 __global__ __launch_bounds__(512, 2) void rank_bf16_big_kernel(OEA_RANK_BF16_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) float big_lds[];                // BIG_LDS_BYTES
-    rank_bf16_body<false, CSLS, 0, 8, MODE>(OEA_RANK_BF16_ARGS, big_lds, nullptr);
+    rank_bf16_body<false, CSLS, 0, 8, PF>(OEA_RANK_BF16_ARGS, big_lds, nullptr);
 }
 
 // ONE grid-stride prologue: both bf16 packs, the gold similarities (the exact k-ordered chain), the max row norms of both
@@ -3421,7 +3163,7 @@ struct CslsPlan {
 constexpr int kCslsFb = 128, kCslsSlow = 64;
 
 // big: the sweep runs on 256-candidate tiles with 8 waves (csls_append_kernel<.., 8>): chunks count those tiles, 8 segments per chunk
-static CslsPlan plan_csls(int64_t n1, int64_t n2, int k, int big = 0 /* candidate rows of a big tile: 0, 256 or 192 */) {
+static CslsPlan plan_csls(int64_t n1, int64_t n2, int k, int big = 0 /* candidate rows of a big tile: 0 or 256 */) {
     CslsPlan p;
     if (n1 < 4096 || n2 < 4096 || k > 32) return p;
     p.sample = std::max(n1, n2) >= 32768 ? 4096 : 1024;       // keeps r n / S, the survivors per row, in the low hundreds
@@ -3469,7 +3211,6 @@ static int pack_operand_bf16(int slot, const float *src, int64_t n, int ld, int 
 namespace oea {
 // kNN strips (topk.hip): both operands packed once (slot 0 = queries, slot 1 = candidates), every strip produced from
 // the packed copies; release_packed_rows() after the last strip
-bool tile_glds_enabled() { return use_glds(); }
 int pack_rows(int slot, const float *src, int64_t n, int ld, int dim, hipStream_t st, float **packed, int *kp) {
     PackedOp op;
     const int rc = pack_operand(slot, src, n, ld, dim, st, &op);
@@ -3486,7 +3227,7 @@ void sim_inner_store_packed(const float *e1p, int64_t n1, const float *e2p, int6
 // -> number of segments per query (4 * chunks); chunks is chosen here so that the grid fills the chip
 void sim_inner_store_packed_gated(const float *e1p, int64_t n1, const float *e2p, int64_t n2, int kp, int dim, float *out,
                                   int64_t ld_out, const int32_t *gate, hipStream_t st) {
-    sim_inner_store_kernel<true><<<dim3((unsigned)ceil_div(n2, TILE), (unsigned)ceil_div(n1, TILE)), 256, 0, st>>>(
+    sim_inner_store_kernel<<<dim3((unsigned)ceil_div(n2, TILE), (unsigned)ceil_div(n1, TILE)), 256, 0, st>>>(
         e1p, n1, kp, e2p, n2, kp, dim, out, ld_out, gate);
 }
 int topk_append_chunks(int64_t nq, int64_t nc) {
@@ -3496,10 +3237,10 @@ int topk_append_chunks(int64_t nq, int64_t nc) {
 void topk_append_sym_packed(const float *ep, int64_t n, int kp, int dim, const float *thr, const void *items, int n_items, int nseg,
                             int cap, float *list_vals, int32_t *list_cols, int32_t *counts, int T, int ccap, void *clists,
                             uint8_t *ccounts, int32_t *spill_cnt, void *spill, int sp_cap, hipStream_t st) {
-    topk_append_sym_kernel<true, false><<<(unsigned)n_items, 256, 0, st>>>(ep, n, kp, dim, thr, static_cast<const int4 *>(items), nseg,
-                                                                           cap, list_vals, list_cols, counts, T, ccap,
-                                                                           static_cast<uint2 *>(clists), ccounts, spill_cnt,
-                                                                           static_cast<uint2 *>(spill), sp_cap, nullptr);
+    topk_append_sym_kernel<false><<<(unsigned)n_items, 256, 0, st>>>(ep, n, kp, dim, thr, static_cast<const int4 *>(items), nseg,
+                                                                     cap, list_vals, list_cols, counts, T, ccap,
+                                                                     static_cast<uint2 *>(clists), ccounts, spill_cnt,
+                                                                     static_cast<uint2 *>(spill), sp_cap, nullptr);
 }
 // stream form (topk_stream_sym_kernel): rows split and packed into slot 3, the bound into tol_dev[0], one launch
 int topk_stream_sym_bf16(const float *src, int64_t n, int ld, int dim, const float *thr, const void *items, int n_items, void *row_streams,
@@ -3546,7 +3287,7 @@ int topk_append_sym_bf16(const float *src, int64_t n, int ld, int dim, const flo
     OEA_CHECK_HIP(hipMemsetAsync(tol_dev, 0, 8, st));
     row_norm_max_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(src, n, ld, dim, reinterpret_cast<unsigned *>(tol_dev) + 1);
     knn_tol_kernel<<<1, 1, 0, st>>>(tol_dev, bf16_eps_rel(dim, false));
-    topk_append_sym_kernel<true, true><<<(unsigned)n_items, 256, 0, st>>>(op.p, n, op.kp, dim, thr, static_cast<const int4 *>(items), nseg,
+    topk_append_sym_kernel<true><<<(unsigned)n_items, 256, 0, st>>>(op.p, n, op.kp, dim, thr, static_cast<const int4 *>(items), nseg,
                                                                           cap, list_vals, list_cols, counts, T, ccap,
                                                                           static_cast<uint2 *>(clists), ccounts, spill_cnt,
                                                                           static_cast<uint2 *>(spill), sp_cap, tol_dev);
@@ -3556,7 +3297,7 @@ void topk_append_packed(const float *qp, int64_t nq, const float *cp, int64_t nc
                         int chunks, float *list_vals, int32_t *list_cols, int32_t *counts, int32_t *spill_cnt, void *spill, int sp_cap,
                         hipStream_t st) {
     const int tpc = (int)ceil_div(ceil_div(nc, TILE), chunks);       // chunks planned by topk_append_chunks
-    topk_append_kernel<true><<<dim3((unsigned)ceil_div(nq, TILE), (unsigned)chunks), 256, 0, st>>>(
+    topk_append_kernel<false><<<dim3((unsigned)ceil_div(nq, TILE), (unsigned)chunks), 256, 0, st>>>(
         qp, nq, kp, cp, nc, kp, dim, thr, tpc, cap, list_vals, list_cols, counts, spill_cnt, static_cast<uint2 *>(spill), sp_cap);
 }
 // the neighbour search's sample strip on the bf16 split (round 6; the CSLS means' strips since round 5): a threshold is an ESTIMATE of where
@@ -3598,8 +3339,8 @@ void topk_append_bf16_launch(const float *qs, int64_t nq, const float *cs, int64
     static const bool breg = [] { const char *e = getenv("OEA_TOPK_STREAM_NCH"); return !(e && e[0] == '0'); }();
     const dim3 grid((unsigned)ceil_div(nq, TILE), (unsigned)chunks);
 #define OEA_APPEND_LAUNCH(N)                                                                                                             \
-    topk_append_kernel<true, true, N><<<grid, 256, 0, st>>>(qs, nq, kp, cs, nc, kp, dim, thr, tpc, cap, list_vals, list_cols, counts, spill_cnt, \
-                                                            static_cast<uint2 *>(spill), sp_cap, tol_dev)
+    topk_append_kernel<true, N><<<grid, 256, 0, st>>>(qs, nq, kp, cs, nc, kp, dim, thr, tpc, cap, list_vals, list_cols, counts, spill_cnt, \
+                                                      static_cast<uint2 *>(spill), sp_cap, tol_dev)
     if (breg && kp == 128) OEA_APPEND_LAUNCH(4);
     else if (breg && kp == 96) OEA_APPEND_LAUNCH(3);
     else OEA_APPEND_LAUNCH(0);
@@ -3635,26 +3376,18 @@ int oea_rank_eval(const float *e1, int64_t n1, int32_t ld1, const float *e2, int
         const int64_t qt = oea::ceil_div(n1, TILE), ctiles = oea::ceil_div(n2, TILE);
         const int chunks = pick_chunks(qt, ctiles, &tpc);
         const dim3 grid((unsigned)qt, (unsigned)chunks);
-        if (use_glds()) {
-            PackedOp p1, p2;
-            int rc = pack_operand(0, e1, n1, ld1, dim, st, &p1);
-            if (rc == OEA_OK) rc = pack_operand(1, e2, n2, ld2, dim, st, &p2);
-            if (rc != OEA_OK) return rc;
-            if (csls_r)
-                rank_inner_kernel<true, true><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc,
-                                                                    gold_offset, rank, keys, EvalTail{});
-            else
-                rank_inner_kernel<false, true><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc,
-                                                                     gold_offset, rank, keys, EvalTail{});
-            rc = release_packed(st);
-            if (rc != OEA_OK) return rc;
-        } else if (csls_r) {
-            rank_inner_kernel<true, false><<<grid, 256, 0, st>>>(e1, n1, ld1, e2, n2, ld2, dim, gold, csls_r, csls_c, tpc, gold_offset,
-                                                                 rank, keys, EvalTail{});
-        } else {
-            rank_inner_kernel<false, false><<<grid, 256, 0, st>>>(e1, n1, ld1, e2, n2, ld2, dim, gold, csls_r, csls_c, tpc, gold_offset,
-                                                                  rank, keys, EvalTail{});
-        }
+        PackedOp p1, p2;
+        int rc = pack_operand(0, e1, n1, ld1, dim, st, &p1);
+        if (rc == OEA_OK) rc = pack_operand(1, e2, n2, ld2, dim, st, &p2);
+        if (rc != OEA_OK) return rc;
+        if (csls_r)
+            rank_inner_kernel<true><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc, gold_offset,
+                                                          rank, keys, EvalTail{});
+        else
+            rank_inner_kernel<false><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc, gold_offset,
+                                                           rank, keys, EvalTail{});
+        rc = release_packed(st);
+        if (rc != OEA_OK) return rc;
     } else if (metric == OEA_METRIC_MANHATTAN || metric == OEA_METRIC_EUCLIDEAN) {
         const int64_t qt = oea::ceil_div(n1, VT), ctiles = oea::ceil_div(n2, VT);
         const int chunks = pick_chunks(qt, ctiles, &tpc);
@@ -3757,13 +3490,7 @@ static int rank_eval_bf16_impl(const float *e1, int64_t n1, int32_t ld1, const f
     static const bool big_on = [] { const char *e = getenv("OEA_BF16_BIG"); return !(e && e[0] == '0'); }();
     const bool big = big_on && p1.kp > 128;
     const int nw = big ? 8 : 4;
-    // OEA_BF16_BIG_MODE: 1 (default) = all 8 waves multiply, fragment reads one MFMA group ahead; 2 = 6 multiplying + 2 loading waves on
-    // 192-candidate tiles (measured equal: 35.3 against 34.7 ms at 70,000^2 x 1,200); 0 = the first form; the
-    // CSLS-terms-in-the-epilogue variant (rare) keeps mode 0
-    static const int big_mode_env = [] { const char *e = getenv("OEA_BF16_BIG_MODE"); return e ? atoi(e) : 1; }();
-    const int big_mode = sweep_r ? 0 : big_mode_env;
-    const int big_mt = big_mode == 2 ? SPEC_MT : BIG_MT;
-    const int chunks = pick_chunks(qt, big ? oea::ceil_div(n2, big_mt) : ctiles, &tpc);
+    const int chunks = pick_chunks(qt, big ? oea::ceil_div(n2, BIG_MT) : ctiles, &tpc);
     const int64_t n_waves = (int64_t)nw * qt * chunks;
     const unsigned slice_cap = (unsigned)(cap / std::max<int64_t>(n_waves, 1));
     if (n_waves > bf16_max_waves(n1) || slice_cap < 32) {
@@ -3793,24 +3520,22 @@ static int rank_eval_bf16_impl(const float *e1, int64_t n1, int32_t ld1, const f
         else if (nch == 1) OEA_BF16_LAUNCH((rank_bf16_breg_kernel<W, C, 1>), GRID, TPC);                \
         else OEA_BF16_LAUNCH((rank_bf16_kernel<W, C>), GRID, TPC);                                      \
     } while (0)
-#define OEA_BF16_BIG_SWEEP(C, M)                                                                                                     \
+#define OEA_BF16_BIG_SWEEP(C, PF)                                                                                                    \
     do {                                                                                                                            \
         /* the attribute belongs to (function, DEVICE): set on every call (cheap), not once per process */             \
-        OEA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rank_bf16_big_kernel<C, M>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+        OEA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rank_bf16_big_kernel<C, PF>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                           BIG_LDS_BYTES));                                                                          \
-        rank_bf16_big_kernel<C, M><<<tile_grid_blocks(gs), 512, BIG_LDS_BYTES, st>>>(p1.p, n1, p1.kp, p2.p, n2, dim_p, gold, tol, sweep_r, sweep_c, tpc, \
+        rank_bf16_big_kernel<C, PF><<<tile_grid_blocks(gs), 512, BIG_LDS_BYTES, st>>>(p1.p, n1, p1.kp, p2.p, n2, dim_p, gold, tol, sweep_r, sweep_c, tpc, \
                                                                                      gold_offset, rank, lbrow, rec, rec_cnt, slice_cap, gs);    \
         OEA_CHECK_HIP(hipGetLastError());                                                                                           \
     } while (0)
     if (sweep_r) {
         if (warm >= 2) OEA_BF16_SWEEP(true, true, gw, warm);
-        if (big) OEA_BF16_BIG_SWEEP(true, 0);          // (CSLS terms in the epilogue -- only when the two extra coordinates would cost a
+        if (big) OEA_BF16_BIG_SWEEP(true, false);      // (CSLS terms in the epilogue -- only when the two extra coordinates would cost a
         else OEA_BF16_SWEEP(false, true, gs, tpc);     //  chunk: the prefetched forms spill there)
     } else {
         if (warm >= 2) OEA_BF16_SWEEP(true, false, gw, warm);
-        if (big && big_mode == 2) OEA_BF16_BIG_SWEEP(false, 2);
-        else if (big && big_mode == 1) OEA_BF16_BIG_SWEEP(false, 1);
-        else if (big) OEA_BF16_BIG_SWEEP(false, 0);
+        if (big) OEA_BF16_BIG_SWEEP(false, true);
         else OEA_BF16_SWEEP(false, false, gs, tpc);
     }
 #undef OEA_BF16_BIG_SWEEP
@@ -3839,7 +3564,6 @@ int oea_rank_eval_bf16(const float *e1, int64_t n1, int32_t ld1, const float *e2
     OEA_REQUIRE(n1 >= 0 && gold_offset >= 0 && n1 + gold_offset <= n2, "gold of row i is column gold_offset + i <= n2");
     OEA_REQUIRE(ld1 % 4 == 0 && ld2 % 4 == 0 && dim > 0 && dim <= ld1 && dim <= ld2, "ld % 4 == 0, dim <= ld");
     OEA_REQUIRE(n2 < 0x7fffffff && n1 < 0x7fffffff, "n < 2^31");
-    OEA_REQUIRE(use_glds(), "the bf16 prefilter runs on the packed (LDS-DMA) tile path");
     hipStream_t st = oea::as_stream(stream);
     if (n1 == 0) { OEA_CHECK_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st)); return OEA_OK; }
     return rank_eval_bf16_impl(e1, n1, ld1, e2, n2, ld2, dim, nullptr, nullptr, gold_offset, nullptr, 0, rank, argmax, nullptr, status,
@@ -3854,7 +3578,6 @@ int oea_rank_eval_bf16_csls(const float *e1, int64_t n1, int32_t ld1, const floa
     OEA_REQUIRE(n1 >= 0 && gold_offset >= 0 && n1 + gold_offset <= n2, "gold of row i is column gold_offset + i <= n2");
     OEA_REQUIRE(ld1 % 4 == 0 && ld2 % 4 == 0 && dim > 0 && dim <= ld1 && dim <= ld2, "ld % 4 == 0, dim <= ld");
     OEA_REQUIRE(n2 < 0x7fffffff && n1 < 0x7fffffff, "n < 2^31");
-    OEA_REQUIRE(use_glds(), "the bf16 prefilter runs on the packed (LDS-DMA) tile path");
     hipStream_t st = oea::as_stream(stream);
     if (n1 == 0) { OEA_CHECK_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st)); return OEA_OK; }
     return rank_eval_bf16_impl(e1, n1, ld1, e2, n2, ld2, dim, csls_r, csls_c, gold_offset, nullptr, 0, rank, argmax, nullptr, status,
@@ -3869,7 +3592,6 @@ int oea_rank_eval_metrics_bf16(const float *e1, int64_t n1, int32_t ld1, const f
     OEA_REQUIRE(n1 > 0 && gold_offset >= 0 && n1 + gold_offset <= n2, "gold of row i is column gold_offset + i <= n2");
     OEA_REQUIRE(ld1 % 4 == 0 && ld2 % 4 == 0 && dim > 0 && dim <= ld1 && dim <= ld2, "ld % 4 == 0, dim <= ld");
     OEA_REQUIRE(n2 < 0x7fffffff && n1 < 0x7fffffff && nk >= 1 && nk <= 8, "n < 2^31, 1 <= len(top_k) <= 8");
-    OEA_REQUIRE(use_glds(), "the bf16 prefilter runs on the packed (LDS-DMA) tile path");
     return rank_eval_bf16_impl(e1, n1, ld1, e2, n2, ld2, dim, csls_r, csls_c, gold_offset, top_k_host, nk, rank, argmax,
                                reinterpret_cast<long long *>(out_dev), nullptr, workspace, oea::as_stream(stream));
 }
@@ -3877,7 +3599,6 @@ int oea_rank_eval_metrics_bf16(const float *e1, int64_t n1, int32_t ld1, const f
 int oea_sim_bf16_matrix(const float *e1, int64_t n1, int32_t ld1, const float *e2, int64_t n2, int32_t ld2, int32_t dim, float *out,
                         int64_t ld_out, void *stream) {
     OEA_REQUIRE(e1 && e2 && out && ld_out >= n2 && dim > 0 && dim <= ld1 && dim <= ld2 && ld1 % 4 == 0 && ld2 % 4 == 0, "arguments");
-    OEA_REQUIRE(use_glds(), "packed tile path only");
     if (n1 == 0 || n2 == 0) return OEA_OK;
     hipStream_t st = oea::as_stream(stream);
     PackedOp p1, p2;
@@ -3919,7 +3640,6 @@ int oea_rank_eval_metrics(const float *e1, int64_t n1, int32_t ld1, const float 
     OEA_REQUIRE(ld1 % 4 == 0 && ld2 % 4 == 0 && dim > 0 && dim <= ld1 && dim <= ld2, "ld % 4 == 0, dim <= ld");
     OEA_REQUIRE((csls_r == nullptr) == (csls_c == nullptr), "csls_r and csls_c go together");
     OEA_REQUIRE(n2 < 0x7fffffff && nk >= 1 && nk <= 8, "n2 < 2^31, 1 <= len(top_k) <= 8");
-    if (!use_glds()) { oea::set_error("oea_rank_eval_metrics needs the packed-operand tiles (OEA_TILE_GLDS=0 is set)"); return OEA_EUNSUPPORTED; }
     hipStream_t st = oea::as_stream(stream);
     unsigned long long *keys = static_cast<unsigned long long *>(workspace);
     float *gold = reinterpret_cast<float *>(keys + n1);
@@ -3948,11 +3668,11 @@ int oea_rank_eval_metrics(const float *e1, int64_t n1, int32_t ld1, const float 
     const int chunks = pick_chunks(qt, ctiles, &tpc);
     const dim3 grid((unsigned)qt, (unsigned)chunks);
     if (csls_r)
-        rank_inner_kernel<true, true><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc,
-                                                            gold_offset, rank, keys, tail);
+        rank_inner_kernel<true><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc,
+                                                      gold_offset, rank, keys, tail);
     else
-        rank_inner_kernel<false, true><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc,
-                                                             gold_offset, rank, keys, tail);
+        rank_inner_kernel<false><<<grid, 256, 0, st>>>(p1.p, n1, p1.kp, p2.p, n2, p2.kp, dim, gold, csls_r, csls_c, tpc,
+                                                       gold_offset, rank, keys, tail);
     rc = release_packed(st);
     if (rc != OEA_OK) return rc;
     OEA_CHECK_HIP(hipGetLastError());
@@ -3965,7 +3685,7 @@ int oea_sim_matrix(const float *e1, int64_t n1, int32_t ld1, const float *e2, in
     OEA_REQUIRE(ld1 % 4 == 0 && ld2 % 4 == 0 && dim > 0 && dim <= ld1 && dim <= ld2 && ld_out >= n2 && ld_out < (1 << 24), "shapes");
     if (n1 == 0 || n2 == 0) return OEA_OK;
     hipStream_t st = oea::as_stream(stream);
-    if (metric == OEA_METRIC_INNER && use_glds()) {
+    if (metric == OEA_METRIC_INNER) {
         PackedOp p1, p2;
         int rc = pack_operand(0, e1, n1, ld1, dim, st, &p1);
         if (rc == OEA_OK) rc = pack_operand(1, e2, n2, ld2, dim, st, &p2);
@@ -3973,9 +3693,6 @@ int oea_sim_matrix(const float *e1, int64_t n1, int32_t ld1, const float *e2, in
         launch_store_packed(p1.p, n1, p2.p, n2, p1.kp, dim, out, ld_out, st);
         rc = release_packed(st);
         if (rc != OEA_OK) return rc;
-    } else if (metric == OEA_METRIC_INNER) {
-        sim_inner_store_kernel<false><<<dim3((unsigned)oea::ceil_div(n2, TILE), (unsigned)oea::ceil_div(n1, TILE)), 256, 0, st>>>(
-            e1, n1, ld1, e2, n2, ld2, dim, out, ld_out, nullptr);
     } else if (metric == OEA_METRIC_MANHATTAN) {
         sim_valu_store_kernel<OEA_METRIC_MANHATTAN><<<dim3((unsigned)oea::ceil_div(n2, VT), (unsigned)oea::ceil_div(n1, VT)), 256, 0, st>>>(
             e1, n1, ld1, e2, n2, ld2, dim, out, ld_out);
@@ -4078,8 +3795,8 @@ int oea_row_topk_mean(const float *s, int64_t n1, int64_t n2, int64_t ld, int32_
 }
 
 size_t oea_csls_means_workspace_bytes(int64_t n1, int64_t n2, int32_t k) {
-    const CslsPlan p = plan_csls(n1, n2, k), pb = plan_csls(n1, n2, k, BIG_MT), ps = plan_csls(n1, n2, k, SPEC_MT);   // (the call picks one by the row width)
-    return p.ok ? std::max(p.total, std::max(pb.ok ? pb.total : 0, ps.ok ? ps.total : 0)) : 0;
+    const CslsPlan p = plan_csls(n1, n2, k), pb = plan_csls(n1, n2, k, BIG_MT);   // (the call picks one by the row width)
+    return p.ok ? std::max(p.total, pb.ok ? pb.total : 0) : 0;
 }
 
 int oea_csls_means(const float *e1, int64_t n1, int32_t ld1, const float *e2, int64_t n2, int32_t ld2, int32_t dim, int32_t k,
@@ -4095,11 +3812,9 @@ int oea_csls_means(const float *e1, int64_t n1, int32_t ld1, const float *e2, in
     const double bf16_min = env_min ? atof(env_min) : 3e8;
     const bool bf16 = bf16_on && (double)n1 * (double)n2 >= bf16_min;
     static const bool big_on = [] { const char *e = getenv("OEA_BF16_BIG"); return !(e && e[0] == '0'); }();
-    static const int big_mode = [] { const char *e = getenv("OEA_BF16_BIG_MODE"); return e ? atoi(e) : 1; }();
-    const int big_mt = big_mode == 2 ? SPEC_MT : BIG_MT;
-    const bool big = bf16 && big_on && (dim + BK - 1) / BK * BK > 128 && plan_csls(n1, n2, k, big_mt).ok;
-    const CslsPlan p = plan_csls(n1, n2, k, big ? big_mt : 0);
-    if (!p.ok || !use_glds()) { oea::set_error("oea_csls_means: shape not covered (n1, n2 >= 4096, k <= 32, packed tiles)"); return OEA_EUNSUPPORTED; }
+    const bool big = bf16 && big_on && (dim + BK - 1) / BK * BK > 128 && plan_csls(n1, n2, k, BIG_MT).ok;
+    const CslsPlan p = plan_csls(n1, n2, k, big ? BIG_MT : 0);
+    if (!p.ok) { oea::set_error("oea_csls_means: shape not covered (n1, n2 >= 4096, k <= 32)"); return OEA_EUNSUPPORTED; }
     OEA_REQUIRE(ws_bytes >= p.total, "workspace smaller than oea_csls_means_workspace_bytes");
     hipStream_t st = oea::as_stream(stream);
     char *w = static_cast<char *>(workspace);
@@ -4157,21 +3872,14 @@ int oea_csls_means(const float *e1, int64_t n1, int32_t ld1, const float *e2, in
         row_norm_max_kernel<<<(unsigned)oea::ceil_div(n2, 256), 256, 0, st>>>(e2, n2, ld2, dim, reinterpret_cast<unsigned *>(tol) + 2);
         csls_tol_kernel<<<1, 1, 0, st>>>(tol, bf16_eps_rel(dim, true));
         static const bool breg_on = [] { const char *e = getenv("OEA_BF16_BREG"); return !(e && e[0] == '0'); }();
-#define OEA_CSLS_APPEND(N) csls_append_kernel<true, true, N><<<tile_grid_blocks(grid), 256, 0, st>>>(b1.p, n1, kp, b2.p, n2, kp, dim, thr1, thr2, p.tpc, \
+#define OEA_CSLS_APPEND(N) csls_append_kernel<true, N><<<tile_grid_blocks(grid), 256, 0, st>>>(b1.p, n1, kp, b2.p, n2, kp, dim, thr1, thr2, p.tpc, \
                                                                                                    p.cap, p.ccap, qlists, qcnt, clists, ccnt, tol, grid)
         if (big) {
-#define OEA_CSLS_BIG(M)                                                                                                              \
-            do {                                                                                                                    \
-                OEA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(csls_append_kernel<true, true, 0, 8, M>),           \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES));   /* per device */   \
-                csls_append_kernel<true, true, 0, 8, M><<<tile_grid_blocks(grid), 512, BIG_LDS_BYTES, st>>>(                        \
-                    b1.p, n1, kp, b2.p, n2, kp, dim, thr1, thr2, p.tpc, p.cap, p.ccap, qlists, qcnt, clists, ccnt, tol, grid);      \
-                OEA_CHECK_HIP(hipGetLastError());                                                                                   \
-            } while (0)
-            if (big_mode == 2) OEA_CSLS_BIG(2);
-            else if (big_mode == 1) OEA_CSLS_BIG(1);
-            else OEA_CSLS_BIG(0);
-#undef OEA_CSLS_BIG
+            OEA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(csls_append_kernel<true, 0, 8>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS_BYTES));   // per device
+            csls_append_kernel<true, 0, 8><<<tile_grid_blocks(grid), 512, BIG_LDS_BYTES, st>>>(
+                b1.p, n1, kp, b2.p, n2, kp, dim, thr1, thr2, p.tpc, p.cap, p.ccap, qlists, qcnt, clists, ccnt, tol, grid);
+            OEA_CHECK_HIP(hipGetLastError());
         } else switch ((breg_on && kp <= 128) ? kp / 32 : 0) {
             case 4: OEA_CSLS_APPEND(4); break;
             case 3: OEA_CSLS_APPEND(3); break;
@@ -4185,7 +3893,7 @@ int oea_csls_means(const float *e1, int64_t n1, int32_t ld1, const float *e2, in
         list_mean_rows_kernel<true><<<(unsigned)oea::ceil_div(n2, 4), 256, 0, st>>>(clists, ccnt, 2 * p.nqt, p.ccap, n2, k, c_out, fail2,
                                                                                     nfail + 1, e2, ld2, e1, ld1, dim, thr2, tol);
     } else {
-        csls_append_kernel<true, false><<<tile_grid_blocks(grid), 256, 0, st>>>(p1.p, n1, kp, p2.p, n2, kp, dim, thr1, thr2, p.tpc, p.cap, p.ccap,
+        csls_append_kernel<false><<<tile_grid_blocks(grid), 256, 0, st>>>(p1.p, n1, kp, p2.p, n2, kp, dim, thr1, thr2, p.tpc, p.cap, p.ccap,
                                                                                  qlists, qcnt, clists, ccnt, nullptr, grid);
         list_mean_rows_kernel<false><<<(unsigned)oea::ceil_div(n1, 4), 256, 0, st>>>(qlists, qcnt, p.nseg, p.cap, n1, k, r_out, fail1, nfail,
                                                                                      nullptr, 0, nullptr, 0, 0, nullptr, nullptr);
@@ -4194,11 +3902,11 @@ int oea_csls_means(const float *e1, int64_t n1, int32_t ld1, const float *e2, in
     }
     // fallbacks (normally empty): bulk for the first kCslsFb failed rows / columns, slow kernel for the rest
     oea::gather_packed_rows(p1.p, kp, fail1, nfail, fbq, st);
-    sim_inner_store_kernel<true><<<dim3((unsigned)oea::ceil_div(n2, TILE), 1), 256, 0, st>>>(fbq, kCslsFb, kp, p2.p, n2, kp, dim, strip, p.ld2, nfail);
+    sim_inner_store_kernel<<<dim3((unsigned)oea::ceil_div(n2, TILE), 1), 256, 0, st>>>(fbq, kCslsFb, kp, p2.p, n2, kp, dim, strip, p.ld2, nfail);
     row_topk_mean_kernel<<<kCslsFb / 4, 256, 0, st>>>(strip, kCslsFb, n2, p.ld2, k, r_out, fail1, nfail);
     slow_mean_rows_kernel<<<kCslsSlow, 256, 0, st>>>(e1, ld1, e2, n2, ld2, dim, k, r_out, fail1, nfail, kCslsFb, scratch, p.ld2);
     oea::gather_packed_rows(p2.p, kp, fail2, nfail + 1, fbq, st);
-    sim_inner_store_kernel<true><<<dim3((unsigned)oea::ceil_div(n1, TILE), 1), 256, 0, st>>>(fbq, kCslsFb, kp, p1.p, n1, kp, dim, strip, p.ld1, nfail + 1);
+    sim_inner_store_kernel<<<dim3((unsigned)oea::ceil_div(n1, TILE), 1), 256, 0, st>>>(fbq, kCslsFb, kp, p1.p, n1, kp, dim, strip, p.ld1, nfail + 1);
     row_topk_mean_kernel<<<kCslsFb / 4, 256, 0, st>>>(strip, kCslsFb, n1, p.ld1, k, c_out, fail2, nfail + 1);
     slow_mean_rows_kernel<<<kCslsSlow, 256, 0, st>>>(e2, ld2, e1, n1, ld1, dim, k, c_out, fail2, nfail + 1, kCslsFb, scratch, p.ld1);
     rc = release_packed(st);

@@ -61,7 +61,7 @@ def greedy_alignment_device(t1, t2, dim, top_k, metric, normalize, csls_k):
     r = c = grid = None
     if csls_k > 0:
         r, c, grid = csls_means_device(t1, t2, dim, kmetric, csls_k, return_grid=True)
-    if kmetric == 'inner' and 1 <= len(top_k) <= 8 and ops.tile_glds():
+    if kmetric == 'inner' and 1 <= len(top_k) <= 8:
         if ops.eval_bf16_enabled(t1.shape[0], t2.shape[0]):
             # certified bf16 prefilter (with or without the CSLS means): the same ranks / nearest candidates at 3/16 of the fp32
             # matrix time; None = its record buffer overflowed (tables of near-duplicates): the fp32 sweep below

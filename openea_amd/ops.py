@@ -665,7 +665,7 @@ def eval_bf16_enabled(n1, n2):
     datasets do not win back inside greedy_alignment (bench r04k: 34.7 vs 38.5 M pairs/s), the 70,000 of the 100K datasets do
     (11.6 vs 7.5 M pairs/s).  OEA_EVAL_BF16=0 keeps the fp32 sweep, OEA_EVAL_BF16_MIN_PAIRS moves the limit."""
     lim = float(os.environ.get('OEA_EVAL_BF16_MIN_PAIRS', '3e8'))
-    return os.environ.get('OEA_EVAL_BF16', '1')[:1] != '0' and tile_glds() and n1 * n2 >= lim
+    return os.environ.get('OEA_EVAL_BF16', '1')[:1] != '0' and n1 * n2 >= lim
 
 
 def rank_eval(e1, e2, dim, metric='inner', csls_r=None, csls_c=None, gold_offset=0, allow_bf16=True):
@@ -864,13 +864,6 @@ def rank_eval_l1_grid(e1, e2, dim, gold_offset=0, block_bytes=2 << 30, csls_r=No
     return rank, argmax
 
 
-def tile_glds():
-    """the similarity tiles run on packed operands staged by LDS-DMA (default; OEA_TILE_GLDS=0 selects the register-staged
-    pipeline, kept for the bit-exactness test between the two)"""
-    import os
-    return os.environ.get("OEA_TILE_GLDS", "1")[:1] != "0"
-
-
 def rank_eval_metrics(e1, e2, dim, top_k, csls_r=None, csls_c=None, gold_offset=0):
     """inner-product evaluation in two launches (oea_rank_eval_metrics) + ONE device->host copy ->
     (rank int32 [n1] device, argmax int32 [n1] device, hits counts list[int], rank_sum int, rr_sum float)."""
@@ -959,7 +952,7 @@ def csls_means(e1, e2, dim, k):
     """one-sweep CSLS means (oea_csls_means) -> (r [n1], c [n2]) or None when the shape is not covered"""
     n1, n2 = e1.shape[0], e2.shape[0]
     nbytes = lib().oea_csls_means_workspace_bytes(n1, n2, int(k))
-    if nbytes == 0 or not _lib.tile_glds():
+    if nbytes == 0:
         return None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=e1.device)
     r = torch.empty(n1, dtype=torch.float32, device=e1.device)
