@@ -279,6 +279,24 @@ int oea_transr_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float
                     float *rel_matrix_acc, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg,
                     int64_t n_neg, const oea_step_cfg *cfg, void *step_workspace, void *transr_workspace, double *loss_accum,
                     void *stream);
+/* The semantic-matching models' step (models/semantic/{hole,simple}.py), one wave per positive and its k negatives:
+ *   OEA_SEMANTIC_HOLE    u = l2n(ent)[e], rh = l2n(l2n(rel)[r]) (normalised twice, hole.py:57), c = ccorr(uh, ut) with
+ *                        c[k] = sum_i uh[i] ut[(i + k) mod dim], score = -sigmoid(rh . c),
+ *                        loss = sum_p relu(margin + score_p - mean_j score_{p,j}) (hole.py:41-86);
+ *   OEA_SEMANTIC_SIMPLE  ent = [H; T] (2E rows), rel = [R1; R2] (2R rows), each row l2-normalised, triple ids in [0, E) / [0, R),
+ *                        score = (l2n(H[h] o R1[r]) . T[t] + l2n(H[t] o R2[r]) . T[h]) / 2,
+ *                        loss = sum_pos softplus(-score) + sum_neg softplus(score) (simple.py:39-88).
+ * neg[p k .. p k + k) are the k = cfg->neg_group_k >= 1 corruptions of pos p (the device sampler's layout), n_neg == k n_pos.
+ * cfg: margin (HolE), neg_group_k, ent_l2_norm / rel_l2_norm, opt_kind SGD or Adagrad, lr; score_kind stays OEA_SCORE_TRANSE and
+ * loss_kind is not read (the model brings its own).  The row gradients go into the step workspace's scratch (entity rows, relation
+ * copy 0; a row that a positive shares with its negatives as one summed row) and the call ends with
+ * oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY); step_workspace: as for oea_triple_step with (n_ent, n_rel) = the table
+ * rows.  Unknown model, Adam / Adadelta, dim > 128: OEA_EUNSUPPORTED; n_neg != k n_pos, ld % 4 != 0: OEA_EINVAL -- both before
+ * anything is launched.  loss_accum += the batch loss. */
+enum { OEA_SEMANTIC_HOLE = 0, OEA_SEMANTIC_SIMPLE = 1 };
+int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
+                      int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg,
+                      const oea_step_cfg *cfg, void *step_workspace, double *loss_accum, void *stream);
 /* addresses of the entity gradient scratch and its touched flags inside a step workspace */
 int oea_step_entity_scratch(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, void **ent_grad,
                             void **ent_touched);

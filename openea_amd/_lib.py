@@ -168,6 +168,8 @@ PROTOTYPES = {
     "oea_transr_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
     "oea_transr_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
                                   _vp, _vp, _vp, _vp]),
+    "oea_semantic_step": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
+                                    _vp, _vp, _vp]),
     "oea_greedy_matching": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "oea_pair_dots": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "oea_perm_index": (_u32, [_u32, _u32, _u32]),

@@ -249,6 +249,21 @@ def transr_step(ent, ent_acc, rel, rel_acc, rel_matrix, rel_matrix_acc, dim, pos
                                 _p(workspace), _p(transr_ws), _p(loss_accum), _stream()))
 
 
+# ---- HolE / SimplE ----------------------------------------------------------------------------------------------
+SEMANTIC_HOLE, SEMANTIC_SIMPLE = 0, 1
+SEMANTIC_MAX_DIM = 128
+
+
+def semantic_step(model, ent, ent_acc, rel, rel_acc, dim, pos, neg, cfg, workspace, loss_accum):
+    """One HolE / SimplE optimiser step in place (oea_semantic_step): model SEMANTIC_HOLE or SEMANTIC_SIMPLE (stacked tables:
+    ent = [H; T], rel = [R1; R2]); neg [n * k, 3] with neg[p*k:(p+1)*k] the corruptions of pos p, k = cfg.neg_group_k; the
+    batch loss is added to `loss_accum`."""
+    n_neg = 0 if neg is None else neg.shape[0]
+    check(lib().oea_semantic_step(int(model), _p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim,
+                                  ent.shape[1], _p(pos), pos.shape[0], _p(neg), n_neg, C.byref(cfg), _p(workspace),
+                                  _p(loss_accum), _stream()))
+
+
 def part_rows_per_rank(n_ent, world):
     return int(lib().oea_part_rows_per_rank(int(n_ent), int(world)))
 
