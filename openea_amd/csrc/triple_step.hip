@@ -2009,25 +2009,33 @@ void launch_wave(int nb, int block, hipStream_t st, const float *ent, const floa
 #undef OEA_WAVE
 }
 
-// the rule of triple_wave (and of the epoch plan that builds on it)
+// OEA_STEP_RUNTIME_KIND=1 (experiments): triple_grouped with the run-time switch of loss kind and norm, everywhere
+static bool step_runtime_kind() {
+    static const int env = [] { const char *e = getenv("OEA_STEP_RUNTIME_KIND"); return e ? atoi(e) : 0; }();
+    return env != 0;
+}
+
+// THE rule of triple_wave, and with it of the epoch plan: only triple_wave stores a positive's rows into the plan's contrib and
+// honours its pflags, so launch_grouped (wave or grouped kernel) and oea_step_plan_supported (plan or no plan) both ask here and
+// nowhere else.  One wave per positive: the per-triple "limited" loss on normalised rows, 1..10 grouped negatives, rows of at most
+// 256 columns, tables whose byte offsets fit the instruction's 32-bit scalar offset.
 static bool wave_rule(const oea_step_cfg &cfg, int64_t n_ent, int64_t n_rel, int32_t ld) {
     return cfg.score_kind == OEA_SCORE_TRANSE && cfg.loss_kind == OEA_LOSS_LIMITED && cfg.ent_l2_norm && cfg.rel_l2_norm &&
            cfg.neg_group_k >= 1 && cfg.neg_group_k <= 10 && ld <= 256 &&
-           std::max(n_ent, n_rel) * (int64_t)ld * (int64_t)sizeof(grad_t) < ((int64_t)1 << 30) && step_wave_enabled();
+           std::max(n_ent, n_rel) * (int64_t)ld * (int64_t)sizeof(grad_t) < ((int64_t)1 << 30) && step_wave_enabled() &&
+           !step_runtime_kind();
 }
 
 template <int G, int IT>
 void launch_grouped(int nb, int block, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
-                    int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, bool wave_fits, float *contrib = nullptr,
+                    int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, bool wave, float *contrib = nullptr,
                     const uint32_t *pflags = nullptr) {
-    static const int runtime_kind = [] { const char *e = getenv("OEA_STEP_RUNTIME_KIND"); return e ? atoi(e) : 0; }();
+    const bool runtime_kind = step_runtime_kind();
     const int k = cfg.neg_group_k;
-    // one wave per positive (round 6): the per-triple losses with a compile-time kind, rows of at most 256 columns, tables whose
-    // byte offsets fit the instruction's 32-bit scalar offset; same grid as triple_grouped with blocks of (256 / G) waves, so the
-    // number of loss partials is launch_step's nb1 either way
+    // one wave per positive (round 6) where wave_rule says so (wave = its answer; ld <= 256 are exactly the instances below): same
+    // grid as triple_grouped with blocks of (256 / G) waves, so the number of loss partials is launch_step's nb1 either way
     if constexpr ((G == 32 && IT <= 4) || (G == 64 && IT == 4)) {
-        if (wave_fits && !runtime_kind && cfg.loss_kind == OEA_LOSS_LIMITED && cfg.ent_l2_norm && cfg.rel_l2_norm && k >= 0 && k <= 10 &&
-            step_wave_enabled()) {
+        if (wave) {
             constexpr int IT64 = G == 32 ? (IT + 1) / 2 : 4;
             // G == 32 (ld <= 128): the grid has one workgroup per 8 positives (launch_step's rule for the loss partials).  512 threads =
             // one positive per wave; 256 threads = two per wave (grid stride): half the waves, nearly all resident at once, and
@@ -2093,8 +2101,7 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
         else if (transh)
             oea::launch_timed(triple_transh_grouped<G, IT>, nb1, block, st, ent, rel, ld, pos, n_pos, neg, n_neg ? cfg.neg_group_k : 0, cfg, ws);
         else if (grouped)
-            launch_grouped<G, IT>(nb1, block, st, ent, rel, ld, pos, n_pos, neg, cfg, ws,
-                                  std::max(n_ent, n_rel) * (int64_t)ld * (int64_t)sizeof(grad_t) < ((int64_t)1 << 30),
+            launch_grouped<G, IT>(nb1, block, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, wave_rule(cfg, n_ent, n_rel, ld),
                                   plan ? plan->contrib : nullptr, plan ? plan->pflags + plan_first_pos : nullptr);
         else
             oea::launch_timed(triple_generic<G, IT>, nb1, block, st, ent, rel, ld, pos, n_pos, neg, n_neg, cfg, ws);

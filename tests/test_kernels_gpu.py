@@ -1536,7 +1536,9 @@ def test_planned_epochs_equal_the_atomic_epochs(tmp_path):
     an ordered gather in the optimiser) against OEA_STEP_PLAN=0 (every gradient row through the atomic scratch): whole epochs,
     ranges that cross epoch boundaries (the plan of the next epoch is sorted on the side stream), a neighbour refresh in the
     middle of an epoch (prepared negatives and plan dropped, the rest of that epoch sampled step by step).  The two differ in the
-    ORDER of fp32 additions only: tables within 2e-6 of their norm, loss within 1e-6."""
+    ORDER of fp32 additions only: tables within 2e-6 of their norm, loss within 1e-6.
+    (Planned against atomic, never against the oracle, and with 32-lane groups only: tests/test_step_plan_gpu.py compares the planned
+    step with the oracle in every dispatch.)"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
