@@ -422,8 +422,12 @@ int oea_epoch_layout(const int32_t *triples, int64_t n1, int64_t n2, const int64
  *   oea_step_plan_bytes      workspace of a plan for n_total positives in `steps` batches of at most max_batch rows (includes the
  *                            2 * max_batch contribution rows)
  *   oea_step_plan_build      pos_all [n_total, 3] in batch order, neg_all [n_total * k, 3] (oea_sample_negatives_epoch), offsets_dev
- *                            [steps + 1] int64 on the device; a few launches + three device primitives on `stream`, no allocation,
- *                            no host read: meant for a side stream behind the previous epoch
+ *                            [steps + 1] int64 on the device; a few launches + four device primitives on `stream`, no allocation,
+ *                            no host read: meant for a side stream behind the previous epoch.  Also leaves rel_order: every
+ *                            step's positives (index inside the batch) in stable ascending order of relation id.  The planned
+ *                            scoring kernel takes its positives in that order, so that a workgroup's 8 waves nearly always
+ *                            share one relation and sum their relation rows on chip before ONE row of atomics
+ *                            (OEA_STEP_REL_ORDER=0: batch order, one row of atomics per positive)
  *   oea_triple_epoch_range_plan  = oea_triple_epoch_range with the plan workspace; plan_built = 0: the call builds the plan itself
  *                            (on `stream`, after drawing the negatives when it draws them); plan == NULL or an unsupported
  *                            configuration: exactly oea_triple_epoch_range. */
@@ -437,6 +441,9 @@ int oea_step_plan_build(const int32_t *pos_all, const int32_t *neg_all, int32_t 
  * [7] total bytes, [8] per-positive hub bits (uint32 [n_total]: bit 0 / 1 = the positive's head / tail row has more than 8
  * references in its step and takes this positive's gradient through the atomic scratch instead); out has 9 elements */
 int oea_step_plan_offsets(int64_t n_total, int32_t steps, int64_t max_batch, int64_t n_ent, int32_t ld, int64_t *out);
+/* *out = byte offset of rel_order (uint32 [n_total]; for step s, rel_order[offsets[s] + i] = index inside the batch of the step's
+ * i-th positive in stable ascending order of relation id = numpy.argsort(relations of the batch, kind="stable")) */
+int oea_step_plan_rel_order_offset(int64_t n_total, int32_t steps, int64_t max_batch, int64_t n_ent, int32_t ld, int64_t *out);
 int oea_triple_epoch_range_plan(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
                                 int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
                                 const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,

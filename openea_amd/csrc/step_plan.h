@@ -14,7 +14,12 @@
 //     instead of streaming the whole table past the touched flags;
 //   * relation rows (a few hundred, shared by the whole batch), the corrupted rows of ACTIVE negatives, positives outside the rule
 //     (mixed sides, foreign entries) and HUB rows (more than kPlanHubEntries references in a step) keep the atomic scratch + touched
-//     flags and the flag-driven optimiser pass.
+//     flags and the flag-driven optimiser pass;
+//   * the relation rows are the largest of the atomic streams that remain (one row per positive).  rel_order lists every step's
+//     positives in stable ascending order of relation id; triple_wave maps its wave slots to positives through it, so the 8 waves
+//     of a workgroup nearly always hold ONE relation, sum their rows through LDS and issue one row of atomics per (workgroup,
+//     relation) instead of one per positive (19,825 -> ~3,100 rows per step at the 100K shape).  Only the wave-to-positive mapping
+//     follows the order: contrib, pflags, the negatives and the plan's lists stay keyed by the batch index.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -36,8 +41,10 @@ struct StepPlanView {
     uint8_t *inplan;               // [steps][n_ent] 1 = the row is summed from the plan in that step (listed and not a hub): the flag-driven
                                    //     part of the optimiser kernel leaves it alone
     float *contrib;                // [2 * max_batch][ld]
-    void *temp;
+    void *temp;                    // the device primitives' temporary storage; before them the relation sort borrows it as its second buffer ([N] uint32)
     size_t temp_bytes;
+    uint32_t *rel_order;           // [N] per step s: rel_order[offsets[s] + i] = index INSIDE the batch of the step's i-th positive in stable
+                                   //     ascending order of relation id (numpy: argsort(pos[offsets[s]:offsets[s + 1], 1], kind="stable"))
     int row_bits;
 };
 

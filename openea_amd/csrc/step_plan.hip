@@ -1,5 +1,5 @@
 // step_plan.hip -- builds the gathered-sum plan of a translational epoch (step_plan.h) from the epoch's positives and the negatives
-// drawn ahead for them.  Five launches + three rocPRIM calls into a caller-provided workspace: nothing is allocated, nothing is read
+// drawn ahead for them.  Six launches + three rocPRIM calls into a caller-provided workspace: nothing is allocated, nothing is read
 // back, so the whole build can sit on a side stream behind the previous epoch (models/trainer.py:_prefetch_next).
 //
 // Replaces nothing of the reference by itself: it is the bookkeeping TF's gradient of tf.nn.embedding_lookup does implicitly
@@ -45,8 +45,10 @@ size_t step_plan_layout(int64_t n_total, int32_t steps, int64_t max_batch, int64
                                      (int32_t *)nullptr, (hipStream_t)0);
     (void)rocprim::exclusive_scan(nullptr, t3, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, m + 1, rocprim::plus<uint32_t>(),
                                   (hipStream_t)0);
-    w.temp_bytes = std::max(t1, std::max(t2, t3)) + 256;
+    const size_t n1 = (size_t)std::max<int64_t>(n_total, 1);
+    w.temp_bytes = std::max(std::max(t1, std::max(t2, t3)), al256(4 * n1)) + 256;   // 4 n1: the relation sort's second buffer
     w.temp = take(w.temp_bytes);
+    w.rel_order = (uint32_t *)take(4 * n1);                      // last: every earlier offset is what it was without it
     w.row_bits = bits_for((uint64_t)std::max<int64_t>(n_ent - 1, 1));
     if (v) *v = w;
     return off;
@@ -87,6 +89,115 @@ __global__ void plan_emit_kernel(const int32_t *__restrict__ pos_all, const int3
     vals[2 * p] = 2u * pl + (tails ? 0u : 1u);                        // head row: + A (tail side) / + B (head side)
     keys[2 * p + 1] = sk | (uint64_t)(uint32_t)t;
     vals[2 * p + 1] = 0x80000000u | (2u * pl + (tails ? 1u : 0u));     // tail row: - B (tail side) / - A (head side)
+}
+
+// rel_order: one workgroup per step sorts the step's batch indices by relation id, stably -- an LSD radix sort with 10-bit digits, as
+// many passes as the step's largest relation id has digits (ONE for up to 1,024 relations; the number of relations is not among the
+// build's arguments, so the workgroup finds it).  A pass is a counting sort in which every wave owns a contiguous slice of the
+// batch and its own row of the histogram: (1) the waves count their slices' digits; (2) an exclusive scan in (digit, wave) order
+// turns the counts into each wave's first output slot per digit; (3) every wave walks its slice in order, 64 indices at a time:
+// a lane's rank among the lanes that hold its digit (10 ballots) is its slot past the wave's running offset.  Slices in wave order,
+// groups in slice order, lanes in lane order: stable.  rocPRIM's radix_sort_pairs takes its merge sort at this size (0.8 M 32-bit
+// keys: 24 launches, 210 us per epoch measured -- more than the order saves); this is one launch of `steps` workgroups.
+constexpr int kRelSortWaves = 8, kRelDigitBits = 10, kRelBins = 1 << kRelDigitBits, kRelAhead = 8;
+__global__ __launch_bounds__(kRelSortWaves * 64) void plan_rel_order_kernel(const int32_t *__restrict__ pos_all, const int64_t *__restrict__ offsets,
+                                                                            uint32_t *__restrict__ tmp, uint32_t *__restrict__ rel_order) {
+    __shared__ uint32_t hist[kRelSortWaves][kRelBins];             // counts, then each wave's next output slot per digit
+    __shared__ uint32_t dbase[kRelBins];                           // first slot of every digit
+    __shared__ uint32_t wsum[kRelSortWaves];
+    __shared__ uint32_t rmax;
+    const int64_t first = offsets[blockIdx.x];
+    const uint32_t n = (uint32_t)(offsets[blockIdx.x + 1] - first);
+    if (n == 0) return;
+    const int32_t *rel = pos_all + 3 * first + 1;                  // relation of batch index i: rel[3 i]
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    const uint32_t slice = (n + kRelSortWaves - 1) / kRelSortWaves, c0 = min(w * slice, n), c1 = min(c0 + slice, n);
+    // a wave's slice is walked kRelAhead groups of 64 at a time: the loads of all of them are in flight before the first is used (one
+    // group at a time the walk was a chain of 40 dependent global loads per phase: 100 us per epoch measured, this: see DESIGN 4.1b)
+    const uint32_t groups = (c1 - c0 + 63u) / 64u;                 // uniform per wave: every lane takes part in the ballots
+    if (t == 0) rmax = 0u;
+    int passes = 1;
+    uint32_t *src = nullptr, *dst = nullptr;
+    for (int pass = 0; pass < passes; ++pass) {
+        const int shift = pass * kRelDigitBits;
+        for (uint32_t i = t; i < kRelSortWaves * kRelBins; i += blockDim.x) (&hist[0][0])[i] = 0u;
+        __syncthreads();
+        uint32_t m = 0u;
+        for (uint32_t g0 = 0; g0 < groups; g0 += kRelAhead) {
+            uint32_t r[kRelAhead];
+#pragma unroll
+            for (int u = 0; u < kRelAhead; ++u) {
+                const uint32_t i = c0 + (g0 + u) * 64u + lane;
+                r[u] = i < c1 ? (uint32_t)rel[3 * (int64_t)(src ? src[i] : i)] : 0xffffffffu;
+            }
+#pragma unroll
+            for (int u = 0; u < kRelAhead; ++u)
+                if (c0 + (g0 + u) * 64u + lane < c1) {
+                    m = max(m, r[u]);
+                    atomicAdd(&hist[w][(r[u] >> shift) & (kRelBins - 1)], 1u);
+                }
+        }
+        if (pass == 0) {                                           // the largest relation id of the step decides the number of passes
+            for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+            if (lane == 0) atomicMax(&rmax, m);
+        }
+        __syncthreads();
+        if (pass == 0) {
+            while (passes * kRelDigitBits < 32 && (rmax >> (passes * kRelDigitBits)) != 0u) ++passes;
+            dst = (passes & 1) ? rel_order + first : tmp + first;  // the last pass writes rel_order
+        }
+        // every thread: kRelBins / blockDim.x consecutive digits; counts -> slots past the digit's first, in wave order
+        constexpr int DPT = kRelBins / (kRelSortWaves * 64);
+        uint32_t tot[DPT], mine = 0u;
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) {
+            uint32_t run = 0u;
+            for (int x = 0; x < kRelSortWaves; ++x) { const uint32_t c = hist[x][t * DPT + j]; hist[x][t * DPT + j] = run; run += c; }
+            tot[j] = run;
+            mine += run;
+        }
+        uint32_t inc = mine;                                       // inclusive scan of the threads' totals: wave, then across waves
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, o); if (lane >= (uint32_t)o) inc += y; }
+        if (lane == 63u) wsum[w] = inc;
+        __syncthreads();
+        uint32_t before = inc - mine;
+        for (uint32_t x = 0; x < w; ++x) before += wsum[x];
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) { dbase[t * DPT + j] = before; before += tot[j]; }
+        __syncthreads();
+        for (uint32_t g0 = 0; g0 < groups; g0 += kRelAhead) {
+            uint32_t idx[kRelAhead], dg[kRelAhead];
+#pragma unroll
+            for (int u = 0; u < kRelAhead; ++u) {
+                const uint32_t i = c0 + (g0 + u) * 64u + lane;
+                idx[u] = i < c1 ? (src ? src[i] : i) : 0u;
+                dg[u] = i < c1 ? ((uint32_t)rel[3 * (int64_t)idx[u]] >> shift) & (kRelBins - 1) : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < kRelAhead; ++u) {
+                const bool on = c0 + (g0 + u) * 64u + lane < c1;
+                const uint32_t d = dg[u];
+                unsigned long long same = __ballot(on);
+#pragma unroll
+                for (int b = 0; b < kRelDigitBits; ++b) {
+                    const unsigned long long has = __ballot(on && ((d >> b) & 1u));
+                    same &= ((d >> b) & 1u) ? has : ~has;
+                }
+                if (on) {
+                    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+                    const uint32_t slot = hist[w][d] + dbase[d] + rank;
+                    dst[slot] = idx[u];
+                    __builtin_amdgcn_wave_barrier();               // (the wave's LDS reads above are issued before the update below)
+                    if (rank == 0u) hist[w][d] += (uint32_t)__popcll(same);
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __threadfence_block();                                     // dst is complete: global writes of this workgroup, read by it next
+        __syncthreads();
+        src = dst;
+        dst = (dst == tmp + first) ? rel_order + first : tmp + first;
+    }
 }
 
 __global__ void plan_step_first_kernel(const uint64_t *__restrict__ ukeys, const int32_t *__restrict__ n_unique, int steps, int row_bits,
@@ -192,7 +303,8 @@ size_t oea_step_plan_bytes(int64_t n_total, int32_t steps, int64_t max_batch, in
 /* byte offsets of the arrays a built plan consists of (tests; the optimiser kernel takes them from step_plan_layout):
  * out[0] sorted entry values (uint32 [2 n_total]: sign << 31 | slot), [1] distinct keys (uint64: step << row_bits | row), [2] first
  * entry of every distinct key (uint32 [.. + 1]), [3] number of distinct keys (int32), [4] first distinct key of every step (int32
- * [steps + 1]), [5] contribution rows (float [2 max_batch, ld]), [6] row_bits, [7] total bytes, [8] per-positive hub bits (uint32 [n_total]) */
+ * [steps + 1]), [5] contribution rows (float [2 max_batch, ld]), [6] row_bits, [7] total bytes, [8] per-positive hub bits (uint32 [n_total]).
+ * The relation order (uint32 [n_total]) came later and has its own call, oea_step_plan_rel_order_offset: callers pass an array of 9 here. */
 int oea_step_plan_offsets(int64_t n_total, int32_t steps, int64_t max_batch, int64_t n_ent, int32_t ld, int64_t *out) {
     OEA_REQUIRE(out && n_total >= 0 && steps >= 0 && n_ent > 0 && ld > 0, "arguments");
     oea::StepPlanView v;
@@ -201,6 +313,15 @@ int oea_step_plan_offsets(int64_t n_total, int32_t steps, int64_t max_batch, int
     out[0] = (char *)v.vals_b - base; out[1] = (char *)v.ukeys - base; out[2] = (char *)v.uoff - base;
     out[3] = (char *)v.n_unique - base; out[4] = (char *)v.step_first - base; out[5] = (char *)v.contrib - base;
     out[6] = v.row_bits; out[7] = (int64_t)total; out[8] = (char *)v.pflags - base;
+    return OEA_OK;
+}
+
+int oea_step_plan_rel_order_offset(int64_t n_total, int32_t steps, int64_t max_batch, int64_t n_ent, int32_t ld, int64_t *out) {
+    OEA_REQUIRE(out && n_total >= 0 && steps >= 0 && n_ent > 0 && ld > 0, "arguments");
+    oea::StepPlanView v;
+    char *base = reinterpret_cast<char *>(4096);
+    (void)oea::step_plan_layout(n_total, steps, max_batch, n_ent, ld, base, &v);
+    *out = (char *)v.rel_order - base;
     return OEA_OK;
 }
 
@@ -236,6 +357,8 @@ int oea_step_plan_build(const int32_t *pos_all, const int32_t *neg_all, int32_t 
         OEA_CHECK_HIP(hipMemsetAsync(v.step_first, 0, sizeof(int32_t) * ((size_t)steps + 1), st));
         return OEA_OK;
     }
+    // rel_order first (its second buffer borrows the primitives' temporary storage)
+    oea::plan_rel_order_kernel<<<(unsigned)steps, oea::kRelSortWaves * 64, 0, st>>>(pos_all, offsets_dev, (uint32_t *)v.temp, v.rel_order);
     oea::plan_emit_kernel<<<(unsigned)oea::ceil_div(n_total, 256), 256, 0, st>>>(pos_all, neg_all, k, offsets_dev, steps, n_total, v.row_bits,
                                                                                  v.keys_a, v.vals_a);
     const int end_bit = std::min(64, v.row_bits + oea::bits_for((uint64_t)steps));

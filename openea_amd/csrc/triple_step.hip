@@ -503,8 +503,24 @@ __device__ __forceinline__ void wave_atomic_row(__amdgpu_buffer_rsrc_t rs, int s
         else buf_grad_add(rs, sign * g.v[it], vgt, soff, 0);
     }
 }
+// one relation row of gradient into the scratch copy of positive `p`, and the row's touched flag
+template <int IT>
+__device__ __forceinline__ void wave_rel_row(const StepWs &ws, int dbg, int64_t p, int r, int row_g, int vg, int vgt, const Row<64, IT> &g) {
+    const int copy = (int)(p % kRelCopies);
+    grad_t *rgb = copy == 0 ? ws.rel_grad : ws.rel_extra + (copy - 1) * ws.rel_copy_stride;
+    const __amdgpu_buffer_rsrc_t rs_rg = __builtin_amdgcn_make_buffer_rsrc(rgb, 0, (dbg & 1) ? 0 : kBufRecords, kBufFlags);
+    const __amdgpu_buffer_rsrc_t rs_rt = __builtin_amdgcn_make_buffer_rsrc(ws.rel_touched, 0, (dbg & 4) ? 0 : kBufRecords, kBufFlags);
+    wave_atomic_row<IT>(rs_rg, r * row_g, vg, vgt, g, 1.f);
+    buf_flag_set(rs_rt, r);
+}
 __device__ __forceinline__ float uniform_f(float x) {       // a value every lane holds -> scalar register (uniform branches on it)
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+
+__device__ __forceinline__ double uniform_d(double x) {     // the same for a double: two scalar registers instead of a vector pair
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
 // y = l2_normalize(v) with the sum of squares as a scalar (tf.nn.l2_normalize: v * rsqrt(max(sum v^2, 1e-12)))
@@ -521,17 +537,21 @@ __device__ __forceinline__ void wave_normalize(Row<64, IT> &r) {
 // PLAN (step_plan.h): the positive's two gradient rows A = gacc, B = gpos leave as PLAIN stores into contrib[2 p + {0, 1}] (the
 // epoch's plan tells the optimiser kernel which entity rows add which of them, with which sign, in which order); only the relation
 // row and the corrupted rows of active negatives still go through the atomic scratch.
+// `order` (PLAN only; step_plan.h: rel_order of this step): wave slot q handles positive order[q] -- the step's positives in stable
+// ascending order of relation id, so a workgroup's waves nearly always hold one relation -- and the relation rows of a workgroup are
+// summed in LDS before the atomics.  Everything else is indexed by the positive's batch index as before.  nullptr: slot q handles
+// positive q and every wave issues its own relation row (OEA_STEP_REL_ORDER=0).
 template <int IT, int L1, int KT, bool PLAN>
 __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void triple_wave(
     const float *__restrict__ ent, const float *__restrict__ rel, int ld, const int32_t *__restrict__ pos,
     int64_t n_pos, const int32_t *__restrict__ neg, int k, oea_step_cfg cfg, StepWs ws, int dbg, float *__restrict__ contrib,
-    const uint32_t *__restrict__ pflags) {
+    const uint32_t *__restrict__ pflags, const uint32_t *__restrict__ order) {
     constexpr int G = 64, KC = 10;
     if (KT > 0) k = KT;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wpb = blockDim.x >> 6;                                          // 8 (ld <= 128) or 4 waves: launch_step's groups per block
-    const int64_t w0 = (int64_t)blockIdx.x * wpb + wv, nw = (int64_t)gridDim.x * wpb;
+    const int64_t nw = (int64_t)gridDim.x * wpb;
     const int row_b = ld * 4, row_g = ld << kGradShift;                       // bytes per table row / scratch row
     // dbg (OEA_STEP_WAVE_DBG, experiments only): bit 0 = an empty resource for the scratch (every atomic is issued and dropped), bit 1 =
     // empty resources for the tables (every row load is issued and returns 0), bit 2 = no touched flags
@@ -544,7 +564,8 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
     const int vt = c_last < ld ? c_last * 4 : kBufOob, vgt = c_last < ld ? c_last << kGradShift : kBufOob;
     const float c_neg = L1 ? -cfg.balance : -2.f * cfg.balance;               // dL/dd of an active negative = c_neg * (d or sgn d)
     double loss_local = 0.0;
-    for (int64_t p = w0; p < n_pos; p += nw) {
+    // one positive p on this wave.  Returns -1, or (only with an order) the relation whose row `gacc` is still to be added to the scratch
+    auto score_positive = [&](int64_t p, Row<G, IT> &gacc) -> int {
         const int32_t *pp = pos + 3 * p;
         const int32_t *ng = neg + p * k * 3;
         const int h = pp[0], r = pp[1], t = pp[2];
@@ -575,8 +596,8 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
 #pragma unroll 1
             for (int j = 0; j < k; ++j)
                 ls += score_independent<G, IT>(ent, rel, ld, lane, p, ng[3 * j], ng[3 * j + 1], ng[3 * j + 2], false, cfg, ws, OEA_LOSS_LIMITED, L1);
-            loss_local += ls;
-            continue;
+            loss_local = uniform_d(loss_local + ls);
+            return -1;
         }
         const bool tails = xh == 0;                                     // (k == 0: vacuously)
         int ce[KC];
@@ -591,7 +612,8 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
         wave_normalize<IT>(yh);
         wave_normalize<IT>(yr);
         wave_normalize<IT>(yt);
-        Row<G, IT> u, gacc, gpos;
+        Row<G, IT> u, gpos;
+        int r_sum = -1;
         float sp = 0.f;
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
@@ -670,12 +692,8 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
             }
         }
         if (cpos | anyneg) {
-            const int copy = (int)(p % kRelCopies);
-            grad_t *rgb = copy == 0 ? ws.rel_grad : ws.rel_extra + (copy - 1) * ws.rel_copy_stride;
-            const __amdgpu_buffer_rsrc_t rs_rg = __builtin_amdgcn_make_buffer_rsrc(rgb, 0, (dbg & 1) ? 0 : kBufRecords, kBufFlags);
-            const __amdgpu_buffer_rsrc_t rs_rt = __builtin_amdgcn_make_buffer_rsrc(ws.rel_touched, 0, (dbg & 4) ? 0 : kBufRecords, kBufFlags);
-            wave_atomic_row<IT>(rs_rg, r * row_g, vg, vgt, gacc, 1.f);
-            buf_flag_set(rs_rt, r);
+            if (PLAN && order) r_sum = r;                               // the relation row leaves with the workgroup's sum below
+            else wave_rel_row<IT>(ws, dbg, p, r, row_g, vg, vgt, gacc);
             // without a plan both rows go through the atomic scratch; with one only the rows the plan marks as hubs of this step
             const unsigned via_atomics = PLAN ? pflags[p] : 3u;         // bit 0: head row, bit 1: tail row
             const bool h_full = tails, t_full = !tails;                  // the row that receives the whole sum (the other: the positive's term)
@@ -688,13 +706,64 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
                 buf_flag_set(rs_et, t);
             }
         }
-        loss_local += (double)lsum;
+        loss_local = uniform_d(loss_local + (double)lsum);     // every lane holds it: kept in scalar registers across the next positive
+        return r_sum;
+    };
+    if constexpr (!PLAN) {
+        for (int64_t p = (int64_t)blockIdx.x * wpb + wv; p < n_pos; p += nw) {  // wave slot = positive, grid stride
+            Row<G, IT> gacc;
+            (void)score_positive(p, gacc);
+        }
+    } else {
+        for (int64_t q0 = (int64_t)blockIdx.x * wpb; q0 < n_pos; q0 += nw) {    // uniform per workgroup: the barrier below is legal
+            const int64_t q = q0 + wv;                                          // this wave's slot; its positive is order[q]
+            Row<G, IT> gacc;
+            const int r_sum = q < n_pos ? score_positive(order ? (int64_t)order[q] : q, gacc) : -1;
+            if (!order) continue;                                               // batch order: every wave added its own relation row
+            // Guideline "sum what shares a destination on chip": the workgroup's waves leave (relation, row) in LDS; the first wave
+            // in wave order that holds a relation adds the rows of the later waves that hold it too, in wave order (equal relations
+            // need not be adjacent), and issues ONE row of atomics and ONE flag for the group, into the scratch copy of its own
+            // positive.  Waves past the end, waves inside both margins and waves that scored independent triples (their atomics
+            // are done) bring "no row" (-1).  Any number of waves per workgroup: under OEA_STEP_WAVE_BLOCK=256 a workgroup is 4
+            // waves that take two slots each, and every pass of this loop sums its own 4 rows.
+            __shared__ float s_row[8][IT][64];
+            __shared__ int s_rel[8];
+            // this lane's byte offset inside a 64-float fragment, taken from the register the row loads use and made opaque: the
+            // LDS addresses are formed here, not hoisted out of the loop into registers the scoring code needs (measured: 9 spilled)
+            int lb = v4;
+            asm volatile("" : "+v"(lb));
+            const auto at = [lb](auto *base) { return (decltype(base))((char *)base + lb); };
+            if (lb == 0) s_rel[wv] = r_sum;
+            if (r_sum >= 0) {
+#pragma unroll
+                for (int it = 0; it < IT; ++it) *at(&s_row[wv][it][0]) = gacc.v[it];
+            }
+            __syncthreads();
+            if (r_sum >= 0) {
+                const int held = lb < wpb * 4 ? *at(&s_rel[0]) : -1;         // lane w: the relation wave w holds
+                bool first = true;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) first = first && !(w < wv && __builtin_amdgcn_readlane(held, w) == r_sum);
+                if (first) {
+#pragma unroll
+                    for (int w = 1; w < 8; ++w)
+                        if (w > wv && __builtin_amdgcn_readlane(held, w) == r_sum) {
+#pragma unroll
+                            for (int it = 0; it < IT; ++it) gacc.v[it] += *at(&s_row[w][it][0]);
+                        }
+                    wave_rel_row<IT>(ws, dbg, order[q], r_sum, row_g, vg, vgt, gacc);
+                }
+            }
+            if (q0 + nw < n_pos) __syncthreads();                       // the next pass writes the rows again
+        }
     }
     // one partial per workgroup, fixed order
     __shared__ double sred[8];
-    if (lane == 0) sred[wv] = loss_local;
+    int lz = v4;                                                              // lane 0 by the register that is live anyway: with the
+    if constexpr (PLAN) asm volatile("" : "+v"(lz));                          // combining loop `lane` itself was kept in scratch for this test
+    if (lz == 0) sred[wv] = loss_local;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (wv == 0 && lz == 0) {
         double s = 0.0;
         for (int w = 0; w < wpb; ++w) s += sred[w];
         ws.partials[blockIdx.x] = s;
@@ -1996,13 +2065,13 @@ static bool step_wave_enabled() {
 template <int IT64>
 void launch_wave(int nb, int block, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
                  int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, float *contrib = nullptr,
-                 const uint32_t *pflags = nullptr) {
+                 const uint32_t *pflags = nullptr, const uint32_t *order = nullptr) {
     const int k = cfg.neg_group_k;
     static const int dbg = [] { const char *e = getenv("OEA_STEP_WAVE_DBG"); return e ? atoi(e) : 0; }();
 #define OEA_WAVE(L1, KT)                                                                                                               \
     do {                                                                                                                               \
-        if (contrib) oea::launch_timed(triple_wave<IT64, L1, KT, true>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags);   \
-        else oea::launch_timed(triple_wave<IT64, L1, KT, false>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags);          \
+        if (contrib) oea::launch_timed(triple_wave<IT64, L1, KT, true>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, order);   \
+        else oea::launch_timed(triple_wave<IT64, L1, KT, false>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, nullptr);          \
     } while (0)
     if (k == 10) { if (cfg.l1) OEA_WAVE(1, 10); else OEA_WAVE(0, 10); }
     else { if (cfg.l1) OEA_WAVE(1, 0); else OEA_WAVE(0, 0); }
@@ -2029,7 +2098,7 @@ static bool wave_rule(const oea_step_cfg &cfg, int64_t n_ent, int64_t n_rel, int
 template <int G, int IT>
 void launch_grouped(int nb, int block, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
                     int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, bool wave, float *contrib = nullptr,
-                    const uint32_t *pflags = nullptr) {
+                    const uint32_t *pflags = nullptr, const uint32_t *order = nullptr) {
     const bool runtime_kind = step_runtime_kind();
     const int k = cfg.neg_group_k;
     // one wave per positive (round 6) where wave_rule says so (wave = its answer; ld <= 256 are exactly the instances below): same
@@ -2042,7 +2111,7 @@ void launch_grouped(int nb, int block, hipStream_t st, const float *ent, const f
             // 4-wave workgroups find their slots beside side-stream kernels where 8-wave workgroups starve (OEA_STEP_WAVE_BLOCK)
             static const int blk_env = [] { const char *e = getenv("OEA_STEP_WAVE_BLOCK"); return e ? atoi(e) : 0; }();
             const int wblock = G == 32 ? (blk_env == 256 || blk_env == 512 ? blk_env : 512) : (block / G) * 64;
-            launch_wave<IT64>(nb, wblock, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, contrib, pflags);
+            launch_wave<IT64>(nb, wblock, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, contrib, pflags, order);
             return;
         }
     }
@@ -2100,9 +2169,14 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
             oea::launch_timed(triple_projected<G, IT, OEA_SCORE_TRANSH>, nb1, block, st, ent, rel, ld, pos, n_pos, neg, n_neg, cfg, ws);
         else if (transh)
             oea::launch_timed(triple_transh_grouped<G, IT>, nb1, block, st, ent, rel, ld, pos, n_pos, neg, n_neg ? cfg.neg_group_k : 0, cfg, ws);
-        else if (grouped)
+        else if (grouped) {
+            // OEA_STEP_REL_ORDER=0 (A/B runs): a planned step's waves take the positives in batch order and every wave issues its own
+            // relation row, as before the plan carried rel_order
+            static const bool rel_order_on = [] { const char *e = getenv("OEA_STEP_REL_ORDER"); return !(e && e[0] == '0'); }();
             launch_grouped<G, IT>(nb1, block, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, wave_rule(cfg, n_ent, n_rel, ld),
-                                  plan ? plan->contrib : nullptr, plan ? plan->pflags + plan_first_pos : nullptr);
+                                  plan ? plan->contrib : nullptr, plan ? plan->pflags + plan_first_pos : nullptr,
+                                  plan && rel_order_on ? plan->rel_order + plan_first_pos : nullptr);
+        }
         else
             oea::launch_timed(triple_generic<G, IT>, nb1, block, st, ent, rel, ld, pos, n_pos, neg, n_neg, cfg, ws);
         if (phase == OEA_PHASE_GRAD || dense_opt)

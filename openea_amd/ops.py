@@ -478,6 +478,15 @@ def step_plan_arrays(plan, n_total, steps, max_batch, n_ent, ld):
                 pflags=raw[off[8]: off[8] + 4 * int(n_total)].view(np.uint32).copy())
 
 
+def step_plan_rel_order(plan, n_total, steps, max_batch, n_ent, ld):
+    """host copy of a built plan's rel_order (tests): uint32 [n_total], per step the batch-local indices of its positives in stable
+    ascending order of relation id (oea_step_plan_rel_order_offset)"""
+    off = C.c_int64(0)
+    check(lib().oea_step_plan_rel_order_offset(int(n_total), int(steps), int(max_batch), int(n_ent), int(ld), C.cast(C.byref(off), C.c_void_p)))
+    n = int(n_total)
+    return plan[off.value: off.value + 4 * n].cpu().numpy().view(np.uint32).copy()
+
+
 def step_plan_stats(plan, n_total, steps, max_batch, n_ent, ld):
     """what a built plan looks like (bench detail / experiments): positives outside the rule, references to hub rows, rows and
     entries per step"""
