@@ -264,6 +264,32 @@ int oea_mapping_epoch(float *ent, float *ent_acc, int64_t n_ent, float *rel, flo
                       int32_t ld, int32_t ent_l2_norm, const int32_t *batches, int32_t steps, int64_t n, float *M, float *M_acc,
                       float alpha, float lr, int32_t opt_kind, const oea_step_cfg *cfg, void *workspace, float *work,
                       double *mapping_loss_accum, double *step_loss_accum, void *stream);
+/* SEA's mapping step, fused (approaches/sea.py:73-98,129-145): two dim x dim matrices, a supervised loss in both directions on
+ * the labelled links (l1[i], l2[i]) and a cycle loss in both directions on the unlabelled links (u1[j], u2[j]):
+ *   E = l2_normalize(ent, 1) (if cfg->ent_l2_norm);  L1 = E[l1], L2 = E[l2], U1 = E[u1], U2 = E[u2]
+ *   loss = alpha_1 (|L2 - gl2n(L1 M1)|^2 + |L1 - gl2n(L2 M2)|^2) + alpha_2 (|U1 - gl2n(U1 M1 M2)|^2 + |U2 - gl2n(U2 M2 M1)|^2)
+ * where gl2n is tf.nn.l2_normalize WITHOUT an axis, as the reference calls it: the whole [n, dim] block divided by
+ * sqrt(max(sum of all its squares, 1e-12)).  M1 / M2 [dim, dim] row-major are updated in place by SGD or Adam (cfg->opt_kind, lr,
+ * beta1, beta2, eps, opt_t; M_state = Adam's [m1; v1; m2; v2], 4 dim^2 zeros at the start, NULL for SGD); every block scalar and
+ * every element of the matrix gradients is summed in a fixed order without float atomics: M1 / M2 have the same bits run to run.
+ * The gradients w.r.t. the NORMALISED entity rows are added into ent_grad / ent_touched (oea_step_entity_scratch), an entity that
+ * occurs several times summed, so that oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY) with the same cfg finishes the step.
+ * n_l == 0 or n_u == 0 alone is legal (that half contributes nothing).  Adagrad / Adadelta, dim > 128: OEA_EUNSUPPORTED;
+ * ld % 4 != 0, n_l == n_u == 0: OEA_EINVAL -- both before anything is launched.  work: oea_sea_mapping_workspace_floats(n_l, n_u,
+ * ld, dim) floats, 16-byte aligned, no initialisation needed.  loss_accum += the batch loss. */
+size_t oea_sea_mapping_workspace_floats(int64_t n_l, int64_t n_u, int32_t ld, int32_t dim);
+int oea_sea_mapping_step(const float *ent, int32_t ld, int32_t dim, const int32_t *ids_l1, const int32_t *ids_l2, int64_t n_l,
+                         const int32_t *ids_u1, const int32_t *ids_u2, int64_t n_u, float *M1, float *M2, float *M_state,
+                         float alpha_1, float alpha_2, const oea_step_cfg *cfg, void *ent_grad, void *ent_touched, float *work,
+                         double *loss_accum, void *stream);
+/* A whole mapping epoch of SEA enqueued by ONE call: `steps` x (oea_sea_mapping_step + the apply phase of the step engine with
+ * `cfg`, whose opt_t counts up from cfg->opt_t).  batches: device int32 [steps][l1 (n_l) | l2 (n_l) | u1 (n_u) | u2 (n_u)].
+ * ent_acc / rel_acc: the mapping optimiser's own state ([2, rows, ld] for Adam).  Single process only (the block scalars of a
+ * data-parallel job would need an all-reduce between the phases of every step). */
+int oea_sea_mapping_epoch(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim,
+                          int32_t ld, const int32_t *batches, int32_t steps, int64_t n_l, int64_t n_u, float *M1, float *M2,
+                          float *M_state, float alpha_1, float alpha_2, const oea_step_cfg *cfg, void *workspace, float *work,
+                          double *mapping_loss_accum, double *step_loss_accum, void *stream);
 /* TransR's step (models/trans/transr.py:13-50): x = l2n(ent)[e], y' = l2n(M_r x) with M_r = rel_matrix[r] as a row-major
  * dim x dim matrix, for h and t of the positive and of the negative (each with its own triple's relation), r = l2n(rel)[r]
  * unprojected, loss = sum relu(margin + |h'+r-t'|^2 - |nh'+nr-nt'|^2) over the pairs (pos i, neg i).  The projections run

@@ -230,6 +230,47 @@ def mapping_epoch(ent, ent_acc, rel, rel_acc, dim, ent_l2_norm, batches, mapping
     return work
 
 
+# ---- SEA -------------------------------------------------------------------------------------------------------
+SEA_MAX_DIM = 128
+
+
+def _sea_work(n_l, n_u, ld, dim, work, dev):
+    need = lib().oea_sea_mapping_workspace_floats(int(n_l), int(n_u), int(ld), int(dim))
+    if work is None or work.numel() < need:
+        work = torch.empty(need, dtype=torch.float32, device=dev)
+    return work
+
+
+def sea_mapping_step(ent, dim, ids_l1, ids_l2, ids_u1, ids_u2, m1, m2, m_state, alpha_1, alpha_2, cfg, workspace, n_ent, n_rel,
+                     loss_accum, work=None):
+    """SEA's mapping step (oea_sea_mapping_step): updates `m1` / `m2` (and Adam's `m_state` [4, d, d]) in place and adds the
+    entity-row gradients into the step workspace's scratch; follow with triple_step(..., empty, phase=PHASE_APPLY) under the
+    same cfg.  ids_l* / ids_u*: device int32 vectors (either pair may be empty)."""
+    n_l, n_u = ids_l1.numel(), ids_u1.numel()
+    assert ids_l2.numel() == n_l and ids_u2.numel() == n_u
+    work = _sea_work(n_l, n_u, ent.shape[1], dim, work, ent.device)
+    eg, et = C.c_void_p(), C.c_void_p()
+    check(lib().oea_step_entity_scratch(_p(workspace), n_ent, n_rel, ent.shape[1], C.byref(eg), C.byref(et)))
+    check(lib().oea_sea_mapping_step(_p(ent), ent.shape[1], dim, _p(ids_l1), _p(ids_l2), n_l, _p(ids_u1), _p(ids_u2), n_u, _p(m1),
+                                     _p(m2), _p(m_state), float(alpha_1), float(alpha_2), C.byref(cfg), eg, et, _p(work),
+                                     _p(loss_accum), _stream()))
+    return work
+
+
+def sea_mapping_epoch(ent, ent_acc, rel, rel_acc, dim, batches, n_l, n_u, m1, m2, m_state, alpha_1, alpha_2, cfg, workspace,
+                      mapping_loss, step_loss, work=None):
+    """a whole SEA mapping epoch with one call (oea_sea_mapping_epoch): batches device int32 [steps, 2 n_l + 2 n_u], every row
+    [l1 | l2 | u1 | u2]; cfg.opt_t = the 1-based count of the epoch's first step."""
+    steps = batches.shape[0]
+    assert batches.dim() == 2 and batches.shape[1] == 2 * (n_l + n_u)
+    work = _sea_work(n_l, n_u, ent.shape[1], dim, work, ent.device)
+    check(lib().oea_sea_mapping_epoch(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim, ent.shape[1],
+                                      _p(batches), int(steps), int(n_l), int(n_u), _p(m1), _p(m2), _p(m_state), float(alpha_1),
+                                      float(alpha_2), C.byref(cfg), _p(workspace), _p(work), _p(mapping_loss), _p(step_loss),
+                                      _stream()))
+    return work
+
+
 # ---- TransR ----------------------------------------------------------------------------------------------------
 TRANSR_MAX_DIM = 128
 

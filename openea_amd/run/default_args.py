@@ -45,6 +45,11 @@ _ARGS = {
     "SimplE": dict(embedding_module="SimplE", alignment_module="sharing", dim=100, init="xavier", ent_l2_norm=True,
                    rel_l2_norm=True, neg_sampling="uniform", neg_triple_num=1, learning_rate=0.01, optimizer="Adagrad",
                    batch_size=5000, start_valid=10, eval_metric="inner", eval_norm=True),
+    # run/args/sea_args_15K.json
+    "SEA": dict(embedding_module="SEA", alignment_module="mapping", dim=100, init="normal", ent_l2_norm=True, rel_l2_norm=True,
+                loss_norm="L2", margin=1.5, loss="margin-based", alpha_1=2.5, alpha_2=0.25, neg_sampling="uniform",
+                neg_triple_num=1, learning_rate=0.01, optimizer="Adam", batch_size=5000, start_valid=10, eval_metric="inner",
+                eval_norm=True),
     "GCN_Align": dict(embedding_module="GCN_Align", alignment_module="mapping", dim=100, neg_sampling="uniform",
                       neg_triple_num=5, learning_rate=8, batch_size=5000, test_threads_num=3, eval_metric="manhattan",
                       eval_norm=False, support_number=1, se_dim=100, ae_dim=100, hidden1=100, gamma=3,
@@ -71,6 +76,7 @@ _SCALE_100K = {
     "TransD": dict(batch_size=20000),
     "HolE": dict(batch_size=20000),
     "SimplE": dict(batch_size=20000, start_valid=50),
+    "SEA": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
     "GCN_Align": dict(batch_size=20000, learning_rate=25),
     "AliNet": dict(batch_size=20000, truncated_epsilon=0.995, min_rel_win=15),
     "RDGCN": dict(batch_size=20000, learning_rate=0.001, start_valid=50),
