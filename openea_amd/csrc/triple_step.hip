@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -448,8 +449,10 @@ __global__ __launch_bounds__(256, (IT <= 4 ? 3 : 2)) void triple_grouped(
 //   * the sampler corrupts ONE side per round (batch.py:101-107), so the k negatives of a positive are almost always all tail
 //     corruptions or all head corruptions: one uniform test picks a select-free loop (tail: d = (h + r) - c with h + r computed
 //     once; head: d = (c + r) - t), and gh == gr (tail) / gt == -gr (head) bit for bit, so ONE accumulator serves both rows.
-//     Positives with mixed sides, or with entries that are not corruptions of them at all, are scored as 1 + k independent triples
-//     (score_independent: the same loss and gradient, three rows per triple);
+//     Positives with mixed sides (the sampler's second round, ~0.3 %) take the same two round trips with the side per negative: one
+//     uniform branch picks the expression, the negative's gradient goes to its own row and to the positive's row on the side it kept,
+//     all through the scratch.  Positives with entries that are not corruptions of them at all (the sampler makes none) are scored as
+//     1 + k independent triples (score_independent: the same loss and gradient, three rows per triple);
 //   * lane-strided fragments of 64 columns: ceil(ld / 64) registers per row (2 at d = 100, packed-fp32 instructions) -> ~64 registers.
 // The scalar unit is shared by the CU's four SIMDs (one instruction per cycle): the scalar work per positive (~250 instructions)
 // matters as much as the vector work (~400).
@@ -591,7 +594,7 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
                 xh |= a;
                 xt |= b;
             }
-        if (bad | min(xh, xt)) {                                        // rare: 1 + k independent triples, one copy of the code
+        if (bad) {                                                      // foreign entries (the sampler makes none): 1 + k independent triples
             double ls = score_independent<G, IT>(ent, rel, ld, lane, p, h, r, t, true, cfg, ws, OEA_LOSS_LIMITED, L1);
 #pragma unroll 1
             for (int j = 0; j < k; ++j)
@@ -599,115 +602,217 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
             loss_local = uniform_d(loss_local + ls);
             return -1;
         }
-        const bool tails = xh == 0;                                     // (k == 0: vacuously)
-        int ce[KC];
-        Row<G, IT> yc[KC];
-#pragma unroll
-        for (int j = 0; j < KC; ++j)
-            if (KT == KC || j < k) {
-                ce[j] = tails ? ids[3 * j + 2] : ids[3 * j];
-                wave_load_row<IT>(rs_ent, ce[j] * row_b, v4, vt, yc[j]);
-            }
-        // ---- the positive ------------------------------------------------------------------------------------------------------
-        wave_normalize<IT>(yh);
-        wave_normalize<IT>(yr);
-        wave_normalize<IT>(yt);
-        Row<G, IT> u, gpos;
-        int r_sum = -1;
-        float sp = 0.f;
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            u.v[it] = yh.v[it] + yr.v[it];
-            const float d = u.v[it] - yt.v[it];
-            gpos.v[it] = d;
-            sp += L1 ? fabsf(d) : d * d;
-        }
-        const float xp = oea::wave_sum_uniform(sp) - cfg.pos_margin;  // losses.py:53: relu(s+ - pos_margin)
-        const bool cpos = xp > 0.f;
-        float lsum = cpos ? xp : 0.f;
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            gpos.v[it] = cpos ? (L1 ? sgn(gpos.v[it]) : 2.f * gpos.v[it]) : 0.f;
-            gacc.v[it] = gpos.v[it];
-        }
-        // ---- the negatives: scores first (k independent chains), then hinges in slot order -------------------------------------
-        float sc[KC];
-        if (tails) {
+        if (min(xh, xt)) {
+            // Mixed sides (the sampler's second round draws with the other side's coin: ~0.3 % of positives).  The side is per NEGATIVE:
+            // an entry that keeps the head is a tail corruption (a negative equal to its positive among them, as in the oracle).  The
+            // same two round trips as below and the same expressions, with one wave-uniform branch per negative.
+            unsigned tmask = 0;                                         // bit j: negative j is a tail corruption
+            int ce[KC];
+            Row<G, IT> yc[KC];
 #pragma unroll
             for (int j = 0; j < KC; ++j)
                 if (KT == KC || j < k) {
-                    wave_normalize<IT>(yc[j]);
-                    float s = 0.f;
-#pragma unroll
-                    for (int it = 0; it < IT; ++it) {
-                        const float d = u.v[it] - yc[j].v[it];          // (h + r) - t'
-                        yc[j].v[it] = d;
-                        s += L1 ? fabsf(d) : d * d;
-                    }
-                    sc[j] = oea::wave_sum_uniform(s);
+                    const int nh = ids[3 * j], nt = ids[3 * j + 2];
+                    const bool tl = nh == h;
+                    tmask |= tl ? 1u << j : 0u;
+                    ce[j] = tl ? nt : nh;
+                    wave_load_row<IT>(rs_ent, ce[j] * row_b, v4, vt, yc[j]);
                 }
-        } else {
+            asm volatile("" : "+s"(tmask));                             // (the sides live in this one register, not as ten conditions)
 #pragma unroll
-            for (int j = 0; j < KC; ++j)
-                if (KT == KC || j < k) {
-                    wave_normalize<IT>(yc[j]);
-                    float s = 0.f;
-#pragma unroll
-                    for (int it = 0; it < IT; ++it) {
-                        const float d = yc[j].v[it] + yr.v[it] - yt.v[it];   // (h' + r) - t
-                        yc[j].v[it] = d;
-                        s += L1 ? fabsf(d) : d * d;
-                    }
-                    sc[j] = oea::wave_sum_uniform(s);
-                }
-        }
-        bool anyneg = false;
-        const float sign_c = tails ? -1.f : 1.f;                        // d/d(corrupted row): -g (tail) / +g (head)
-#pragma unroll
-        for (int j = 0; j < KC; ++j)
-            if (KT == KC || j < k) {
-                const float xn = cfg.neg_margin - sc[j];     // losses.py:54: balance * relu(neg_margin - s-)
-                if (xn > 0.f) {
-                    lsum += cfg.balance * xn;
-                    anyneg = true;
-                    Row<G, IT> g;
-#pragma unroll
-                    for (int it = 0; it < IT; ++it) {
-                        g.v[it] = L1 ? c_neg * sgn(yc[j].v[it]) : c_neg * yc[j].v[it];
-                        gacc.v[it] += g.v[it];
-                    }
-                    wave_atomic_row<IT>(rs_eg, ce[j] * row_g, vg, vgt, g, sign_c);
-                    buf_flag_set(rs_et, ce[j]);
-                }
-            }
-        // ---- the positive's rows: tail side gh = gr = gacc, gt = -gpos; head side gr = gacc, gt = -gacc, gh = gpos -----------------
-        if (PLAN) {
-            const __amdgpu_buffer_rsrc_t rs_cb = __builtin_amdgcn_make_buffer_rsrc(contrib, 0, kBufRecords, kBufFlags);
-            const int so = (int)p * 2 * row_b;                          // rows 2 p (A) and 2 p + 1 (B), always written: the plan reads them
+            for (int it = 0; it < IT; ++it)                             // (opaque: nothing below is common code with the one-sided path)
+                asm volatile("" : "+v"(yh.v[it]), "+v"(yr.v[it]), "+v"(yt.v[it]));
+            wave_normalize<IT>(yh);
+            wave_normalize<IT>(yr);
+            wave_normalize<IT>(yt);
+            Row<G, IT> u, gpos;
+            float sp = 0.f;
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
-                const int vo = it < IT - 1 ? v4 + it * 256 : vt;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gacc.v[it]), rs_cb, vo, so, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gpos.v[it]), rs_cb, vo, so + row_b, 0);
+                u.v[it] = yh.v[it] + yr.v[it];
+                const float d = u.v[it] - yt.v[it];
+                gpos.v[it] = d;
+                sp += L1 ? fabsf(d) : d * d;
             }
-        }
-        if (cpos | anyneg) {
-            if (PLAN && order) r_sum = r;                               // the relation row leaves with the workgroup's sum below
-            else wave_rel_row<IT>(ws, dbg, p, r, row_g, vg, vgt, gacc);
-            // without a plan both rows go through the atomic scratch; with one only the rows the plan marks as hubs of this step
-            const unsigned via_atomics = PLAN ? pflags[p] : 3u;         // bit 0: head row, bit 1: tail row
-            const bool h_full = tails, t_full = !tails;                  // the row that receives the whole sum (the other: the positive's term)
-            if ((via_atomics & 1u) && (h_full || cpos)) {
-                wave_atomic_row<IT>(rs_eg, h * row_g, vg, vgt, h_full ? gacc : gpos, 1.f);
+            const float xp = oea::wave_sum_uniform(sp) - cfg.pos_margin;
+            const bool cpos = xp > 0.f;
+            float lsum = cpos ? xp : 0.f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                gpos.v[it] = cpos ? (L1 ? sgn(gpos.v[it]) : 2.f * gpos.v[it]) : 0.f;
+                gacc.v[it] = gpos.v[it];
+            }
+            // No new accumulators: an active negative sends g to its own row AND to the positive's row on the side it kept (+g head /
+            // -g tail), both through the scratch; gacc sums every g for the relation row alone.
+            bool anyneg = false;
+#pragma unroll
+            for (int j = 0; j < KC; ++j)
+                if (KT == KC || j < k) {
+                    const bool tl = (tmask >> j) & 1u;
+                    wave_normalize<IT>(yc[j]);
+                    float s = 0.f;
+                    if (tl) {
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            const float d = u.v[it] - yc[j].v[it];      // (h + r) - t'
+                            yc[j].v[it] = d;
+                            s += L1 ? fabsf(d) : d * d;
+                        }
+                    } else {
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            const float d = yc[j].v[it] + yr.v[it] - yt.v[it];   // (h' + r) - t
+                            yc[j].v[it] = d;
+                            s += L1 ? fabsf(d) : d * d;
+                        }
+                    }
+                    const float xn = cfg.neg_margin - oea::wave_sum_uniform(s);
+                    if (xn > 0.f) {
+                        lsum += cfg.balance * xn;
+                        anyneg = true;
+                        Row<G, IT> g;
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            g.v[it] = L1 ? c_neg * sgn(yc[j].v[it]) : c_neg * yc[j].v[it];
+                            gacc.v[it] += g.v[it];
+                        }
+                        const int pe = tl ? h : t;
+                        const float sign_c = tl ? -1.f : 1.f;
+                        wave_atomic_row<IT>(rs_eg, ce[j] * row_g, vg, vgt, g, sign_c);
+                        buf_flag_set(rs_et, ce[j]);
+                        wave_atomic_row<IT>(rs_eg, pe * row_g, vg, vgt, g, -sign_c);
+                        buf_flag_set(rs_et, pe);
+                    }
+                }
+            // the positive's own term: the plan lists no row of a positive outside its rule (plan_emit_kernel gives them sentinel
+            // keys), so both rows take the scratch and no contrib row is stored
+            if (cpos) {
+                wave_atomic_row<IT>(rs_eg, h * row_g, vg, vgt, gpos, 1.f);
                 buf_flag_set(rs_et, h);
-            }
-            if ((via_atomics & 2u) && (t_full || cpos)) {
-                wave_atomic_row<IT>(rs_eg, t * row_g, vg, vgt, t_full ? gacc : gpos, -1.f);
+                wave_atomic_row<IT>(rs_eg, t * row_g, vg, vgt, gpos, -1.f);
                 buf_flag_set(rs_et, t);
             }
+            loss_local = uniform_d(loss_local + (double)lsum);
+            if (!(cpos | anyneg)) return -1;
+            if (PLAN && order) return r;                                // the relation row leaves with the workgroup's sum
+            wave_rel_row<IT>(ws, dbg, p, r, row_g, vg, vgt, gacc);
+            return -1;
         }
-        loss_local = uniform_d(loss_local + (double)lsum);     // every lane holds it: kept in scalar registers across the next positive
-        return r_sum;
+        // tail side or head side (k == 0: vacuously tails), each a copy of the code below with the side a compile-time constant.  With
+        // the side a run-time value and the mixed-side block in the function, the compiler hoists the ten rows' sums of squares above
+        // the side test -- ten more live registers -- and <2, 0, 10, *> spill 40 B per lane; as two copies they take 61 / 60 VGPRs
+        auto one_sided = [&](auto side) -> int {
+            constexpr bool tails = decltype(side)::value;
+            int ce[KC];
+            Row<G, IT> yc[KC];
+#pragma unroll
+            for (int j = 0; j < KC; ++j)
+                if (KT == KC || j < k) {
+                    ce[j] = tails ? ids[3 * j + 2] : ids[3 * j];
+                    wave_load_row<IT>(rs_ent, ce[j] * row_b, v4, vt, yc[j]);
+                }
+            // ---- the positive ------------------------------------------------------------------------------------------------------
+            wave_normalize<IT>(yh);
+            wave_normalize<IT>(yr);
+            wave_normalize<IT>(yt);
+            Row<G, IT> u, gpos;
+            int r_sum = -1;
+            float sp = 0.f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                u.v[it] = yh.v[it] + yr.v[it];
+                const float d = u.v[it] - yt.v[it];
+                gpos.v[it] = d;
+                sp += L1 ? fabsf(d) : d * d;
+            }
+            const float xp = oea::wave_sum_uniform(sp) - cfg.pos_margin;  // losses.py:53: relu(s+ - pos_margin)
+            const bool cpos = xp > 0.f;
+            float lsum = cpos ? xp : 0.f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                gpos.v[it] = cpos ? (L1 ? sgn(gpos.v[it]) : 2.f * gpos.v[it]) : 0.f;
+                gacc.v[it] = gpos.v[it];
+            }
+            // ---- the negatives: scores first (k independent chains), then hinges in slot order -------------------------------------
+            float sc[KC];
+            if (tails) {
+#pragma unroll
+                for (int j = 0; j < KC; ++j)
+                    if (KT == KC || j < k) {
+                        wave_normalize<IT>(yc[j]);
+                        float s = 0.f;
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            const float d = u.v[it] - yc[j].v[it];          // (h + r) - t'
+                            yc[j].v[it] = d;
+                            s += L1 ? fabsf(d) : d * d;
+                        }
+                        sc[j] = oea::wave_sum_uniform(s);
+                    }
+            } else {
+#pragma unroll
+                for (int j = 0; j < KC; ++j)
+                    if (KT == KC || j < k) {
+                        wave_normalize<IT>(yc[j]);
+                        float s = 0.f;
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            const float d = yc[j].v[it] + yr.v[it] - yt.v[it];   // (h' + r) - t
+                            yc[j].v[it] = d;
+                            s += L1 ? fabsf(d) : d * d;
+                        }
+                        sc[j] = oea::wave_sum_uniform(s);
+                    }
+            }
+            bool anyneg = false;
+            const float sign_c = tails ? -1.f : 1.f;                        // d/d(corrupted row): -g (tail) / +g (head)
+#pragma unroll
+            for (int j = 0; j < KC; ++j)
+                if (KT == KC || j < k) {
+                    const float xn = cfg.neg_margin - sc[j];     // losses.py:54: balance * relu(neg_margin - s-)
+                    if (xn > 0.f) {
+                        lsum += cfg.balance * xn;
+                        anyneg = true;
+                        Row<G, IT> g;
+#pragma unroll
+                        for (int it = 0; it < IT; ++it) {
+                            g.v[it] = L1 ? c_neg * sgn(yc[j].v[it]) : c_neg * yc[j].v[it];
+                            gacc.v[it] += g.v[it];
+                        }
+                        wave_atomic_row<IT>(rs_eg, ce[j] * row_g, vg, vgt, g, sign_c);
+                        buf_flag_set(rs_et, ce[j]);
+                    }
+                }
+            // ---- the positive's rows: tail side gh = gr = gacc, gt = -gpos; head side gr = gacc, gt = -gacc, gh = gpos -----------------
+            if (PLAN) {
+                const __amdgpu_buffer_rsrc_t rs_cb = __builtin_amdgcn_make_buffer_rsrc(contrib, 0, kBufRecords, kBufFlags);
+                const int so = (int)p * 2 * row_b;                          // rows 2 p (A) and 2 p + 1 (B), always written: the plan reads them
+#pragma unroll
+                for (int it = 0; it < IT; ++it) {
+                    const int vo = it < IT - 1 ? v4 + it * 256 : vt;
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gacc.v[it]), rs_cb, vo, so, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gpos.v[it]), rs_cb, vo, so + row_b, 0);
+                }
+            }
+            if (cpos | anyneg) {
+                if (PLAN && order) r_sum = r;                               // the relation row leaves with the workgroup's sum below
+                else wave_rel_row<IT>(ws, dbg, p, r, row_g, vg, vgt, gacc);
+                // without a plan both rows go through the atomic scratch; with one only the rows the plan marks as hubs of this step
+                const unsigned via_atomics = PLAN ? pflags[p] : 3u;         // bit 0: head row, bit 1: tail row
+                const bool h_full = tails, t_full = !tails;                  // the row that receives the whole sum (the other: the positive's term)
+                if ((via_atomics & 1u) && (h_full || cpos)) {
+                    wave_atomic_row<IT>(rs_eg, h * row_g, vg, vgt, h_full ? gacc : gpos, 1.f);
+                    buf_flag_set(rs_et, h);
+                }
+                if ((via_atomics & 2u) && (t_full || cpos)) {
+                    wave_atomic_row<IT>(rs_eg, t * row_g, vg, vgt, t_full ? gacc : gpos, -1.f);
+                    buf_flag_set(rs_et, t);
+                }
+            }
+            loss_local = uniform_d(loss_local + (double)lsum);     // every lane holds it: kept in scalar registers across the next positive
+            return r_sum;
+        };
+        return xh == 0 ? one_sided(std::true_type{}) : one_sided(std::false_type{});
     };
     if constexpr (!PLAN) {
         for (int64_t p = (int64_t)blockIdx.x * wpb + wv; p < n_pos; p += nw) {  // wave slot = positive, grid stride
