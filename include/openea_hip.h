@@ -327,6 +327,62 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
 int oea_step_entity_scratch(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, void **ent_grad,
                             void **ent_touched);
 
+/* ---- IPTransE (approaches/iptranse.py) -----------------------------------------------------------------------------------------
+ * The path half of train_loss (_generate_path_loss, iptranse.py:173-177, scaled by args.path_parm at iptranse.py:179-181):
+ *   path_parm * sum_p (1 / w_p) relu(|x + y - r|^2 + margin - |x + y - r'|^2),  x, y, r, r' rows of Rn = l2n(rel) (rel itself when
+ *   rel_l2_norm == 0); paths int32 [n, 3] = (r_x, r_y, r), neg_rel int32 [n] = r', weight fp32 [n] = w (the kernel multiplies by
+ *   1 / w in fp32, the reference's tf.cast(1 / weight)).
+ * Scores come from the Gram matrix G = Rn Rn^T, the gradient w.r.t. the normalised rows is A Rn for an R x R coefficient matrix A
+ * built with scalar atomics (ten per active pair): two oea_gemm_tn_f32 products instead of O(n dim) row atomics
+ * (csrc/ptranse_step.hip).  The rows of A Rn that an active pair refers to are ADDED to the relation gradient scratch (copy 0) of
+ * the step workspace and their touched flags set; oea_triple_step_phase(..., OEA_PHASE_APPLY) then runs the optimiser.  loss_accum
+ * += the path loss (path_parm included).  path_workspace: oea_path_workspace_bytes(n_rel, ld) bytes, zero-initialised once; the
+ * call leaves its zero part zeroed again.  n == 0 is legal and launches nothing.
+ * n_rel > 2048: OEA_EUNSUPPORTED; ld % 4 != 0, null pointer: OEA_EINVAL -- before anything is launched.  A path id (or r') outside
+ * [0, n_rel) is found on the device: *err_flag = 3 and the batch adds nothing (no loss, no gradient); while *err_flag != 0 every
+ * later batch is left out too -- the caller reads and clears the flag, as with the sampler's err_flag. */
+size_t oea_path_workspace_bytes(int64_t n_rel, int32_t ld);
+int oea_path_grad(const float *rel, int64_t n_rel, int32_t dim, int32_t ld, const int32_t *paths, const int32_t *neg_rel,
+                  const float *weight, int64_t n, float margin, float path_parm, int32_t rel_l2_norm, void *step_workspace,
+                  int64_t n_ent, void *path_workspace, double *loss_accum, int32_t *err_flag, void *stream);
+/* One session.run([train_loss, optimizer]) of launch_ptranse_training_1epo (iptranse.py:250-268): the GRAD phase of the margin
+ * step on (pos i, neg i), oea_path_grad with cfg->margin and cfg->rel_l2_norm, then ONE apply phase on the summed gradient.
+ * loss_accum += triple loss + path_parm * path loss.  cfg: score_kind OEA_SCORE_TRANSE, loss_kind OEA_LOSS_MARGIN; cfg->l1 != 0 or
+ * an optimiser other than SGD / Adagrad: OEA_EUNSUPPORTED (the reference asserts L2 and Adagrad, iptranse.py:140-142); n_rel and ld
+ * as for oea_path_grad.  n_paths == 0: the plain margin step (path_workspace and err_flag may then be NULL).  A path id outside the
+ * table drops the path half of that step only: its triple half still applies (the flag tells the caller). */
+int oea_ptranse_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim, int32_t ld,
+                     const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg, const int32_t *paths,
+                     const int32_t *neg_rel, const float *weight, int64_t n_paths, float path_parm, const oea_step_cfg *cfg,
+                     void *step_workspace, void *path_workspace, double *loss_accum, int32_t *err_flag, void *stream);
+/* The path batches of a whole epoch in one launch (generate_batch, iptranse.py:77-85, for every step): P = (n1 + n2) / steps paths
+ * per step, the first num1 = (int)((double)n1 / (n1 + n2) * P) from KG1's list (paths1 int32 [n1, 3], weight1 fp32 [n1]), the rest
+ * from KG2's.  random.sample(paths, num) = the first num images of a keyed permutation of the list (oea_perm_index, key from
+ * Philox4x32-10(seed; epoch, step, side)): no repeats inside a step and side.  r' = a Philox-uniform element of the relation list of
+ * the KG the path came from (generate_neg_paths, iptranse.py:21-26; it may equal r, the reference does not filter).
+ * out_paths int32 [steps, P, 3], out_neg_rel int32 [steps, P], out_weight fp32 [steps, P].  Reads no table: it can run ahead on a
+ * side stream.  P == 0 launches nothing. */
+int oea_path_sample_epoch(const int32_t *paths1, const float *weight1, int64_t n1, const int32_t *paths2, const float *weight2,
+                          int64_t n2, const int32_t *rels1, int32_t n_rels1, const int32_t *rels2, int32_t n_rels2, int32_t steps,
+                          uint64_t seed, uint32_t epoch, int32_t *out_paths, int32_t *out_neg_rel, float *out_weight, void *stream);
+/* `steps` x oea_ptranse_step enqueued by ONE call (launch_ptranse_training_1epo's loop, iptranse.py:252-268), no host read and no
+ * allocation inside: batch s = rows [offsets_host[s], offsets_host[s + 1]) of pos_all and of neg_buf (the epoch's negatives already
+ * drawn, one per positive: the layout oea_triple_epoch_range takes with side0 == side1 == NULL and k = 1) with the path batch s of
+ * oea_path_sample_epoch's three buffers.  P == 0: plain margin steps. */
+int oea_ptranse_epoch(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim, int32_t ld,
+                      const int32_t *pos_all, const int64_t *offsets_host, int32_t steps, const int32_t *neg_buf,
+                      const int32_t *path_buf, const int32_t *neg_rel_buf, const float *weight_buf, int64_t P, float path_parm,
+                      const oea_step_cfg *cfg, void *step_workspace, void *path_workspace, double *loss_accum, int32_t *err_flag,
+                      void *stream);
+/* One session.run([alignment_loss, alignment_optimizer]) of launch_alignment_training_1epo (iptranse.py:288-301):
+ * loss = sum_i weight[i] relu(|h + r - t|^2 + margin - |h' + r' - t'|^2) over the pairs (pos i, neg i), rows from the
+ * (normalised) tables (_generate_transe_alignment_loss, iptranse.py:167-170); one wave per pair, the gradient rows into the step
+ * scratch with the engine's own atomics, then the apply phase.  cfg: margin, ent_l2_norm / rel_l2_norm, opt_kind SGD or Adagrad, lr;
+ * l1 != 0, Adam / Adadelta: OEA_EUNSUPPORTED.  loss_accum += the batch loss. */
+int oea_weighted_pair_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim,
+                           int32_t ld, const int32_t *pos, const int32_t *neg, const float *weight, int64_t n,
+                           const oea_step_cfg *cfg, void *step_workspace, double *loss_accum, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Negative sampling -- replaces generate_neg_triples_fast (modules/train/batch.py:89-119).
  * The membership set replaces the python set `all_triples_set`.

@@ -176,6 +176,15 @@ PROTOTYPES = {
                                   _vp, _vp, _vp, _vp]),
     "oea_semantic_step": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
                                     _vp, _vp, _vp]),
+    "oea_path_workspace_bytes": (_sz, [_i64, _i32]),
+    "oea_path_grad": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "oea_ptranse_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _f32,
+                                   C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp]),
+    "oea_path_sample_epoch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "oea_ptranse_epoch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _f32,
+                                    C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp]),
+    "oea_weighted_pair_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, C.POINTER(StepCfg), _vp,
+                                         _vp, _vp]),
     "oea_greedy_matching": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "oea_pair_dots": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "oea_perm_index": (_u32, [_u32, _u32, _u32]),

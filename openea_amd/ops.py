@@ -305,6 +305,106 @@ def semantic_step(model, ent, ent_acc, rel, rel_acc, dim, pos, neg, cfg, workspa
                                   _p(loss_accum), _stream()))
 
 
+# ---- IPTransE ---------------------------------------------------------------------------------------------------
+PATH_MAX_REL = 2048
+
+
+def path_workspace(n_rel, ld, dev=None):
+    """scratch of oea_path_grad / oea_ptranse_step for a relation table of n_rel rows (zeroed once; the calls leave its zero part
+    zeroed) + the int32 error flag of the device-side id check: -> (workspace, err_flag)"""
+    dev = dev or device()
+    nbytes = lib().oea_path_workspace_bytes(int(n_rel), int(ld))
+    return torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def path_check(err_flag):
+    """raise if the device-side id check of the path steps found an id outside the relation table (one sync); clears the flag"""
+    code = int(err_flag.item())
+    if code != 0:
+        err_flag.zero_()
+        raise OpenEAHipError("libopenea_hip error %d: a path id outside [0, n_rel) (err_flag %d): the path batch was left out"
+                             % (-1, code))
+
+
+def path_grad(rel, dim, paths, neg_rel, weight, margin, path_parm, rel_l2_norm, workspace, n_ent, path_ws, loss_accum, check_ids=True):
+    """the path half of IPTransE's step (oea_path_grad): adds its gradient w.r.t. the normalised relation rows into the step
+    workspace's scratch and path_parm * path loss to `loss_accum`; follow with triple_step(..., phase=PHASE_APPLY).  paths device
+    int32 [n, 3] = (r_x, r_y, r), neg_rel int32 [n], weight fp32 [n]; path_ws = path_workspace(...).  check_ids: read the id
+    check's flag (one sync) and raise on an id outside the table."""
+    ws, err = path_ws
+    n = paths.shape[0]
+    assert neg_rel.numel() == n and weight.numel() == n
+    check(lib().oea_path_grad(_p(rel), rel.shape[0], dim, rel.shape[1], _p(paths), _p(neg_rel), _p(weight), n, float(margin),
+                              float(path_parm), int(bool(rel_l2_norm)), _p(workspace), int(n_ent), _p(ws), _p(loss_accum), _p(err),
+                              _stream()))
+    if check_ids and n:
+        path_check(err)
+
+
+def ptranse_step(ent, ent_acc, rel, rel_acc, dim, pos, neg, paths, neg_rel, weight, path_parm, cfg, workspace, path_ws, loss_accum,
+                 check_ids=True):
+    """One IPTransE optimiser step in place (oea_ptranse_step): margin pairs (pos i, neg i) + the path batch, one apply phase on
+    the summed gradient; `loss_accum` += triple loss + path_parm * path loss.  paths may be None / empty (plain margin step)."""
+    ws, err = path_ws
+    n_p = 0 if paths is None else paths.shape[0]
+    n_neg = 0 if neg is None else neg.shape[0]
+    check(lib().oea_ptranse_step(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim, ent.shape[1],
+                                 _p(pos), pos.shape[0], _p(neg), n_neg, _p(paths) if n_p else None, _p(neg_rel) if n_p else None,
+                                 _p(weight) if n_p else None, n_p, float(path_parm), C.byref(cfg), _p(workspace), _p(ws),
+                                 _p(loss_accum), _p(err), _stream()))
+    if check_ids and n_p:
+        path_check(err)
+
+
+def path_sample_dims(n1, n2, steps):
+    """-> (P, num1) of a step's path batch (iptranse.py:77, 245)"""
+    P = (n1 + n2) // steps
+    return P, (int(n1 / (n1 + n2) * P) if P else 0)
+
+
+def path_sample_epoch(paths1, weight1, paths2, weight2, rels1, rels2, steps, seed, epoch, out=None):
+    """the path batches of an epoch in one launch (oea_path_sample_epoch) -> (paths [steps, P, 3] int32, neg_rel [steps, P] int32,
+    weight [steps, P] fp32) on the device; paths* int32 [n, 3], weight* fp32 [n], rels* int32 relation lists."""
+    n1, n2 = paths1.shape[0], paths2.shape[0]
+    P, _ = path_sample_dims(n1, n2, steps) if n1 + n2 else (0, 0)
+    dev = paths1.device
+    if out is None or out[0].shape != (steps, P, 3):
+        out = (torch.empty((steps, P, 3), dtype=torch.int32, device=dev), torch.empty((steps, P), dtype=torch.int32, device=dev),
+               torch.empty((steps, P), dtype=torch.float32, device=dev))
+    check(lib().oea_path_sample_epoch(_p(paths1), _p(weight1), n1, _p(paths2), _p(weight2), n2, _p(rels1), rels1.numel(), _p(rels2),
+                                      rels2.numel(), int(steps), int(seed), int(epoch), _p(out[0]), _p(out[1]), _p(out[2]),
+                                      _stream()))
+    return out
+
+
+def ptranse_epoch(ent, ent_acc, rel, rel_acc, dim, pos_all, offsets, neg_all, path_batches, path_parm, cfg, workspace, path_ws,
+                  loss_accum, check_ids=True):
+    """every step of an IPTransE epoch with one call (oea_ptranse_epoch): offsets host int64 [steps + 1] into pos_all / neg_all
+    (one negative per positive, already drawn), path_batches = path_sample_epoch's three buffers (or None: plain margin steps)."""
+    ws, err = path_ws
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    steps = len(offsets) - 1
+    P = 0 if path_batches is None else int(path_batches[0].shape[1])
+    if P:
+        assert path_batches[0].shape[0] == steps
+    pb = path_batches if P else (None, None, None)
+    check(lib().oea_ptranse_epoch(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim, ent.shape[1],
+                                  _p(pos_all), offsets.ctypes.data_as(C.c_void_p), steps, _p(neg_all), _p(pb[0]), _p(pb[1]),
+                                  _p(pb[2]), P, float(path_parm), C.byref(cfg), _p(workspace), _p(ws), _p(loss_accum), _p(err),
+                                  _stream()))
+    if check_ids and P:
+        path_check(err)
+
+
+def weighted_pair_step(ent, ent_acc, rel, rel_acc, dim, pos, neg, weight, cfg, workspace, loss_accum):
+    """One step of IPTransE's alignment loss in place (oea_weighted_pair_step): sum_i weight[i] relu(pos_i + margin - neg_i) over
+    the pairs (pos i, neg i), int32 [n, 3] each, weight fp32 [n]."""
+    n = pos.shape[0]
+    assert neg.shape[0] == n and weight.numel() == n
+    check(lib().oea_weighted_pair_step(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim, ent.shape[1],
+                                       _p(pos), _p(neg), _p(weight), n, C.byref(cfg), _p(workspace), _p(loss_accum), _stream()))
+
+
 def part_rows_per_rank(n_ent, world):
     return int(lib().oea_part_rows_per_rank(int(n_ent), int(world)))
 
