@@ -327,6 +327,39 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
 int oea_step_entity_scratch(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, void **ent_grad,
                             void **ent_touched);
 
+/* ---- ProjE (models/neural/proje.py) --------------------------------------------------------------------------------------------
+ * oea_log_uniform_sample: the candidate sampler of the sampled softmax.  n_sampled DISTINCT classes of [0, n_classes) under the
+ * log-uniform law P(c) = (log(c + 2) - log(c + 1)) / log(n_classes + 1), drawn one after another until n_sampled distinct values
+ * have appeared; out_ids holds them in the order of first appearance, *out_num_tries the (1-based) index of the draw that produced
+ * the last of them, out_log_q_sampled[j] = log Q(out_ids[j]) with Q(c) = -expm1(num_tries log1p(-P(c))) (fp64, stored as fp32).
+ * Draw t of step `step` is a pure function of (seed, step, t): word t & 3 of Philox4x32-10(counter = (t >> 2, 0x50726a45, step lo,
+ * step hi), key = (seed lo, seed hi)), u = (word + 0.5) 2^-32, class = the first c with u < thresholds[c].  thresholds: device fp64
+ * [n_classes], T[c] = log(c + 2) / log(n_classes + 1), built on the host.  All outputs are device pointers.  workspace:
+ * oea_log_uniform_workspace_bytes() bytes, zeroed once; the call leaves it zeroed.  The call waits for the stream (it reads a
+ * status word back).  n_sampled < 1, n_sampled > n_classes, a null pointer: OEA_EINVAL before any launch; more than
+ * 64 n_sampled draws needed: OEA_EUNSUPPORTED (the outputs are then undefined). */
+size_t oea_log_uniform_workspace_bytes(int64_t n_classes, int64_t n_sampled);
+int oea_log_uniform_sample(int64_t n_classes, int64_t n_sampled, uint64_t seed, uint64_t step, const double *thresholds,
+                           int32_t *out_ids, int64_t *out_num_tries, float *out_log_q_sampled, void *workspace, void *stream);
+/* oea_proje_step: forward pass, gradients and TF's dense Adam (oea_adam_dense, beta1 0.9, beta2 0.999, eps 1e-8) of one ProjE batch.
+ * The eight variables with their Adam moments, in this order: ent_embeds [n_ent, ld], rel_embeds [n_rel, ld] (both seen through the
+ * row normalisation), entity_w [n_ent, ld], entity_b [n_ent], input bn beta, mlp_w, mlp_bias, output bn beta [dim].
+ * pos int32 [n_pos, 3]; sampled / log_q_sampled [n_sampled] and num_tries (device int64[1], for log Q of the labels) as
+ * oea_log_uniform_sample wrote them.  phase: OEA_PHASE_GRAD leaves the eight gradients readable through oea_proje_grads (dense
+ * fp32, rows the batch did not touch are zero; the four vectors have stride 128), OEA_PHASE_APPLY runs Adam step t on them.
+ * workspace: oea_proje_workspace_floats(n_ent, n_rel, dim, ld, max_pos, max_sampled) floats, zeroed once, for n_pos <= max_pos and
+ * n_sampled <= max_sampled.  loss_accum += the batch loss.  dim > 128: OEA_EUNSUPPORTED; ld % 4 != 0, n_sampled < 2, n_pos < 1, a
+ * null pointer: OEA_EINVAL -- both before anything is launched.  ids are not checked on the device.  One GPU. */
+typedef struct oea_proje_vars {
+    float *p[8], *m[8], *v[8];
+} oea_proje_vars;
+size_t oea_proje_workspace_floats(int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld, int64_t max_pos, int64_t max_sampled);
+int oea_proje_grads(void *workspace, int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld, int64_t max_pos, int64_t max_sampled,
+                    void **grads);
+int oea_proje_step(const oea_proje_vars *vars, int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
+                   const int32_t *sampled, const float *log_q_sampled, int64_t n_sampled, const int64_t *num_tries, int64_t t, float lr,
+                   void *workspace, int64_t max_pos, int64_t max_sampled, double *loss_accum, int32_t phase, void *stream);
+
 /* ---- IPTransE (approaches/iptranse.py) -----------------------------------------------------------------------------------------
  * The path half of train_loss (_generate_path_loss, iptranse.py:173-177, scaled by args.path_parm at iptranse.py:179-181):
  *   path_parm * sum_p (1 / w_p) relu(|x + y - r|^2 + margin - |x + y - r'|^2),  x, y, r, r' rows of Rn = l2n(rel) (rel itself when

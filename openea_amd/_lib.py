@@ -79,6 +79,11 @@ class RotateCfg(C.Structure):
                 ("rel_l2_norm", C.c_int32), ("opt_kind", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ProjEVars(C.Structure):
+    """mirror of `oea_proje_vars` (include/openea_hip.h): the eight variables, their Adam m and v."""
+    _fields_ = [("p", C.c_void_p * 8), ("m", C.c_void_p * 8), ("v", C.c_void_p * 8)]
+
+
 LOSS_KIND = {"margin-based": 0, "limited": 1, "logistic": 2, "positive": 3, "align": 4}
 OPT_KIND = {"SGD": 0, "Adagrad": 1, "Adam": 2, "Adadelta": 3}
 METRIC = {"inner": 0, "manhattan": 1, "euclidean": 2, "manhattan_f32": 3}
@@ -176,6 +181,12 @@ PROTOTYPES = {
                                   _vp, _vp, _vp, _vp]),
     "oea_semantic_step": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
                                     _vp, _vp, _vp]),
+    "oea_log_uniform_workspace_bytes": (_sz, [_i64, _i64]),
+    "oea_log_uniform_sample": (C.c_int, [_i64, _i64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "oea_proje_workspace_floats": (_sz, [_i64, _i64, _i32, _i32, _i64, _i64]),
+    "oea_proje_grads": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i64, _i64, C.POINTER(C.c_void_p)]),
+    "oea_proje_step": (C.c_int, [C.POINTER(ProjEVars), _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64,
+                                 _i64, _vp, _i32, _vp]),
     "oea_path_workspace_bytes": (_sz, [_i64, _i32]),
     "oea_path_grad": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "oea_ptranse_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _f32,

@@ -31,8 +31,17 @@ def truncated_normal_host(rng, shape, stddev):
 def xavier_host(rng, shape):
     """tf.contrib.layers.xavier_initializer(uniform=False): truncated normal, var = 2/(fan_in+fan_out)
     (initializers.py:22-26)."""
-    std = math.sqrt(2.0 / (shape[0] + shape[1]))
-    return truncated_normal_host(rng, shape, std / 0.87962566103423978)   # TF rescales the truncated std
+    fan = 2 * shape[0] if len(shape) == 1 else shape[0] + shape[1]       # a 1-D shape: fan_in = fan_out = its length
+    std = math.sqrt(2.0 / fan)
+    return truncated_normal_host(rng, tuple(shape), std / 0.87962566103423978)   # TF rescales the truncated std
+
+
+def glorot_uniform_host(rng, shape):
+    """tf.get_variable's default initializer (glorot_uniform): U(-l, l), l = sqrt(6 / (fan_in + fan_out)); a 1-D shape has
+    fan_in = fan_out = its length (proje.py:58-60: mlp_w, mlp_bias)."""
+    fan = 2 * shape[0] if len(shape) == 1 else shape[0] + shape[1]
+    lim = math.sqrt(6.0 / fan)
+    return rng.uniform(-lim, lim, tuple(shape)).astype(np.float32)
 
 
 def unit_host(rng, shape):
@@ -64,6 +73,9 @@ def init_embeddings(shape, name, init, is_l2_norm, dtype=None):
         host = unit_host(_rng, shape)
     else:
         raise ValueError("unknown init %r" % (init,))
+    if len(shape) == 1:                       # a bias vector (proje.py:44): a plain device vector, never normalised
+        from ... import ops
+        return ops.to_vec(host)
     return EmbeddingTable(host, is_l2_norm, name)
 
 

@@ -305,6 +305,87 @@ def semantic_step(model, ent, ent_acc, rel, rel_acc, dim, pos, neg, cfg, workspa
                                   _p(loss_accum), _stream()))
 
 
+# ---- ProjE ------------------------------------------------------------------------------------------------------
+PROJE_MAX_DIM = 128
+PROJE_VARS = ("ent_embeds", "rel_embeds", "entity_w", "entity_b", "input_bn_beta", "mlp_w", "mlp_bias", "output_bn_beta")
+
+
+def log_uniform_thresholds(n_classes, dev=None):
+    """T[c] = log(c + 2) / log(E + 1) in fp64, built on the host: the table oea_log_uniform_sample searches."""
+    t = np.log(np.arange(2, int(n_classes) + 2, dtype=np.float64)) / np.log(np.float64(int(n_classes) + 1))
+    return torch.from_numpy(t).to(dev or device())
+
+
+class LogUniformSampler:
+    """tf.nn.log_uniform_candidate_sampler(unique=True) on the device: sample(step) -> (ids int32 [S] in the order of first
+    appearance, num_tries int64[1], log Q of the ids fp32 [S]); a pure function of (seed, step)."""
+
+    def __init__(self, n_classes, n_sampled, seed, dev=None):
+        dev = dev or device()
+        self.n_classes, self.n_sampled, self.seed = int(n_classes), int(n_sampled), int(seed) & (2 ** 64 - 1)
+        self.thresholds = log_uniform_thresholds(n_classes, dev) if n_classes >= 1 else None
+        nbytes = lib().oea_log_uniform_workspace_bytes(self.n_classes, self.n_sampled)
+        self.workspace = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        self.ids = torch.zeros(max(self.n_sampled, 1), dtype=torch.int32, device=dev)
+        self.num_tries = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.log_q = torch.zeros(max(self.n_sampled, 1), dtype=torch.float32, device=dev)
+
+    def sample(self, step):
+        check(lib().oea_log_uniform_sample(self.n_classes, self.n_sampled, self.seed, int(step), _p(self.thresholds), _p(self.ids),
+                                           _p(self.num_tries), _p(self.log_q), _p(self.workspace), _stream()))
+        return self.ids, self.num_tries, self.log_q
+
+
+def proje_workspace(n_ent, n_rel, dim, ld, max_pos, max_sampled, dev=None):
+    """workspace of proje_step for batches of up to max_pos positives and max_sampled candidates (zeroed once)"""
+    n = lib().oea_proje_workspace_floats(int(n_ent), int(n_rel), int(dim), int(ld), int(max_pos), int(max_sampled))
+    if n == 0:
+        # the shape is refused: the accessor says why
+        check(lib().oea_proje_grads(None, int(n_ent), int(n_rel), int(dim), int(ld), int(max_pos), int(max_sampled), None))
+    ws = torch.zeros(n, dtype=torch.float32, device=dev or device())
+    ws._proje_shape = (int(n_ent), int(n_rel), int(dim), int(ld), int(max_pos), int(max_sampled))
+    return ws
+
+
+def proje_grads(workspace):
+    """the eight dense fp32 gradients a PHASE_GRAD call left in the workspace, as views (order: PROJE_VARS)"""
+    n_ent, n_rel, dim, ld, max_pos, max_s = workspace._proje_shape
+    ptrs = (C.c_void_p * 8)()
+    check(lib().oea_proje_grads(_p(workspace), n_ent, n_rel, dim, ld, max_pos, max_s, ptrs))
+    base = workspace.data_ptr()
+    shapes = [(n_ent, ld), (n_rel, ld), (n_ent, ld), (n_ent,), (dim,), (dim,), (dim,), (dim,)]
+    out = []
+    for ptr, shp in zip(ptrs, shapes):
+        off = (ptr - base) // 4
+        out.append(workspace[off:off + int(np.prod(shp))].view(*shp))
+    return out
+
+
+def proje_step(variables, moments_m, moments_v, dim, pos, sampled, log_q, num_tries, t, lr, workspace, loss_accum,
+               phase=PHASE_BOTH, check_ids=True):
+    """One ProjE step in place (oea_proje_step).  variables / moments_m / moments_v: eight device fp32 tensors each in the order of
+    PROJE_VARS (tables [n, ld], entity_b [n_ent], the four vectors [dim]); pos int32 [n, 3]; sampled, log_q, num_tries as
+    LogUniformSampler.sample returned them.  check_ids: refuse ids outside the tables here (the kernels do not look)."""
+    n_ent, n_rel, wdim, ld, max_pos, max_s = workspace._proje_shape
+    ent, rel = variables[0], variables[1]
+    assert len(variables) == len(moments_m) == len(moments_v) == 8
+    assert ent.shape == (n_ent, ld) and rel.shape == (n_rel, ld) and variables[2].shape == (n_ent, ld) and wdim == dim
+    assert variables[3].numel() == n_ent and all(x.numel() == dim for x in variables[4:])
+    if check_ids and pos.numel():
+        hi = pos.max(dim=0).values.tolist()
+        lo = int(pos.min())
+        if lo < 0 or hi[0] >= n_ent or hi[1] >= n_rel or hi[2] >= n_ent or int(sampled.max()) >= n_ent or int(sampled.min()) < 0:
+            raise OpenEAHipError("proje_step: an id lies outside its table (entities %d, relations %d)" % (n_ent, n_rel))
+    v = _lib.ProjEVars()
+    for i in range(8):
+        v.p[i], v.m[i], v.v[i] = variables[i].data_ptr(), moments_m[i].data_ptr(), moments_v[i].data_ptr()
+    for x in list(variables) + list(moments_m) + list(moments_v):
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+    check(lib().oea_proje_step(C.byref(v), n_ent, n_rel, dim, ld, _p(pos), pos.shape[0], _p(sampled), _p(log_q), sampled.numel(),
+                               _p(num_tries), int(t), float(lr), _p(workspace), max_pos, max_s, _p(loss_accum), int(phase),
+                               _stream()))
+
+
 # ---- IPTransE ---------------------------------------------------------------------------------------------------
 PATH_MAX_REL = 2048
 
