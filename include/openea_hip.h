@@ -217,7 +217,10 @@ int oea_step_scatter_ent_rows(void *workspace, int64_t n_ent, int64_t n_rel, int
  * 193-203): variables re_ent_embeds / im_ent_embeds / rel_embeds are tf.float64 (bootea_rotate.py:50-57),
  *   theta = l2n?(rel)[r] * phase_scale,  (a, b) = (h_re + i h_im) e^{i theta} - (t_re + i t_im),  dist = sum_d |(a, b)_d|,
  *   loss = sum softplus(dist+ - gamma) + sum softplus(gamma - dist-)        (= -sum log sigmoid(score), :59-81)
- * and TF's optimiser semantics (optimizers.py:4-20): Adam moves EVERY row every step.
+ * and TF's optimiser semantics (optimizers.py:4-20): Adam moves EVERY row every step.  The plain RotatE
+ * (models/semantic/rotate.py:74-82) divides the negative half by args.neg_triple_num: cfg->neg_loss_div = k > 1 multiplies every
+ * negative triple's loss term and its gradients by 1.0 / k; 0 and 1 leave the negatives undivided (BootEA_RotatE, the same bits as
+ * before the field had a meaning); a negative value is OEA_EINVAL before anything is launched.
  * ent: [2 n_ent, ld] doubles, rows [0, n_ent) = re_ent_embeds, [n_ent, 2 n_ent) = im_ent_embeds; rel: [n_rel, ld].
  * ent_state / rel_state: Adagrad accumulator [rows, ld] (initial 0.1), or Adam m then v [2, rows, ld] (zeros), NULL for SGD.
  * neg == NULL / n_neg == 0: the positive half alone (alignment loss).  neg_group_k as in oea_step_cfg.
@@ -232,7 +235,7 @@ typedef struct oea_rotate_cfg {
     int32_t ent_l2_norm; /* args.ent_l2_norm (both entity tables) */
     int32_t rel_l2_norm; /* args.rel_l2_norm */
     int32_t opt_kind;    /* OEA_OPT_* */
-    int32_t reserved;
+    int32_t neg_loss_div; /* 0, 1: sum of the negatives' terms; k > 1: that sum / k (rotate.py:81, k = args.neg_triple_num) */
 } oea_rotate_cfg;
 size_t oea_rotate_workspace_bytes(int64_t n_ent, int64_t n_rel, int32_t ld);
 size_t oea_rotate_exchange_doubles(int64_t n_ent, int64_t n_rel, int32_t ld);
@@ -305,21 +308,24 @@ int oea_transr_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float
                     float *rel_matrix_acc, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg,
                     int64_t n_neg, const oea_step_cfg *cfg, void *step_workspace, void *transr_workspace, double *loss_accum,
                     void *stream);
-/* The semantic-matching models' step (models/semantic/{hole,simple}.py), one wave per positive and its k negatives:
+/* The semantic-matching models' step (models/semantic/{hole,simple,distmult}.py), one wave per positive and its k negatives:
  *   OEA_SEMANTIC_HOLE    u = l2n(ent)[e], rh = l2n(l2n(rel)[r]) (normalised twice, hole.py:57), c = ccorr(uh, ut) with
  *                        c[k] = sum_i uh[i] ut[(i + k) mod dim], score = -sigmoid(rh . c),
  *                        loss = sum_p relu(margin + score_p - mean_j score_{p,j}) (hole.py:41-86);
  *   OEA_SEMANTIC_SIMPLE  ent = [H; T] (2E rows), rel = [R1; R2] (2R rows), each row l2-normalised, triple ids in [0, E) / [0, R),
  *                        score = (l2n(H[h] o R1[r]) . T[t] + l2n(H[t] o R2[r]) . T[h]) / 2,
- *                        loss = sum_pos softplus(-score) + sum_neg softplus(score) (simple.py:39-88).
+ *                        loss = sum_pos softplus(-score) + sum_neg softplus(score) (simple.py:39-88);
+ *   OEA_SEMANTIC_DISTMULT u = l2n?(ent)[e], w = l2n?(rel)[r] (by cfg->ent_l2_norm / rel_l2_norm), score = sum_d uh[d] w[d] ut[d],
+ *                        loss = MEAN over the N = n_pos + n_neg labelled triples of softplus(-y score), y = +1 for pos, -1 for neg
+ *                        (distmult.py:43-59, batch.py:generate_triple_label_batch); tables not stacked.
  * neg[p k .. p k + k) are the k = cfg->neg_group_k >= 1 corruptions of pos p (the device sampler's layout), n_neg == k n_pos.
  * cfg: margin (HolE), neg_group_k, ent_l2_norm / rel_l2_norm, opt_kind SGD or Adagrad, lr; score_kind stays OEA_SCORE_TRANSE and
  * loss_kind is not read (the model brings its own).  The row gradients go into the step workspace's scratch (entity rows, relation
  * copy 0; a row that a positive shares with its negatives as one summed row) and the call ends with
  * oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY); step_workspace: as for oea_triple_step with (n_ent, n_rel) = the table
  * rows.  Unknown model, Adam / Adadelta, dim > 128: OEA_EUNSUPPORTED; n_neg != k n_pos, ld % 4 != 0: OEA_EINVAL -- both before
- * anything is launched.  loss_accum += the batch loss. */
-enum { OEA_SEMANTIC_HOLE = 0, OEA_SEMANTIC_SIMPLE = 1 };
+ * anything is launched.  loss_accum += the batch loss (DistMult: the batch mean). */
+enum { OEA_SEMANTIC_HOLE = 0, OEA_SEMANTIC_SIMPLE = 1, OEA_SEMANTIC_DISTMULT = 2 };
 int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
                       int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg,
                       const oea_step_cfg *cfg, void *step_workspace, double *loss_accum, void *stream);

@@ -76,7 +76,7 @@ class RotateCfg(C.Structure):
     """mirror of `oea_rotate_cfg` (include/openea_hip.h)."""
     _fields_ = [("gamma", C.c_double), ("phase_scale", C.c_double), ("lr", C.c_double), ("beta1", C.c_double),
                 ("beta2", C.c_double), ("eps", C.c_double), ("t", C.c_int64), ("ent_l2_norm", C.c_int32),
-                ("rel_l2_norm", C.c_int32), ("opt_kind", C.c_int32), ("reserved", C.c_int32)]
+                ("rel_l2_norm", C.c_int32), ("opt_kind", C.c_int32), ("neg_loss_div", C.c_int32)]
 
 
 class ProjEVars(C.Structure):

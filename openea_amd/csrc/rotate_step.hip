@@ -1,4 +1,5 @@
-// rotate_step.hip -- the RotatE step of BootEA_RotatE (approaches/bootea_rotate.py:50-109,148-158) in fp64 for gfx950.
+// rotate_step.hip -- the RotatE step of BootEA_RotatE (approaches/bootea_rotate.py:50-109,148-158) and of the plain RotatE
+// (models/semantic/rotate.py:52-119) in fp64 for gfx950.
 //
 // Variables (bootea_rotate.py:50-57, all tf.float64): re_ent_embeds / im_ent_embeds [E, d] (l2-normalised per row when
 // args.ent_l2_norm: init_embeddings returns l2_normalize(variable), initializers.py:26) and rel_embeds [R, d] (phases).
@@ -6,7 +7,9 @@
 //     theta = rel[r] * (pi / embedding_range),   (a, b) = (h_re + i h_im) * e^{i theta} - (t_re + i t_im),
 //     dist = sum_d sqrt(a_d^2 + b_d^2),   positives: gamma - dist,  negatives: dist - gamma,
 //     loss = - sum log sigmoid(score)  =  sum softplus(dist+ - gamma) + sum softplus(gamma - dist-)   (bootea_rotate.py:72-81)
-// and the alignment loss is the positive half alone (bootea_rotate.py:148-158).
+// and the alignment loss is the positive half alone (bootea_rotate.py:148-158).  The plain RotatE divides the negative half
+// by args.neg_triple_num (rotate.py:81): cfg.neg_loss_div = k > 1 weights every negative triple's term by 1 / k, the factor
+// entering once per triple at d loss / d dist, ahead of every row the triple's gradient goes to.
 //
 // Layout: the two entity tables are STACKED in one [2E, ld] fp64 array (rows [0, E) real, [E, 2E) imaginary parts: same
 // l2_norm flag, same optimiser), the relation phases are [R, ld].  Kernel 1 (rotate_triples): one G-lane group per
@@ -106,10 +109,11 @@ struct FamilyAcc {
     RowD<G, IT> h_re, h_im, t_re, t_im;
 };
 
-// one triple: loss term returned, entity gradients scattered (or kept in `fam`), d loss / d theta ADDED to gth
+// one triple: loss term returned, entity gradients scattered (or kept in `fam`), d loss / d theta ADDED to gth; `w` is the
+// weight of the triple's term in the loss (1 for a positive, 1 / neg_loss_div for a negative)
 template <int G, int IT, bool ACC>
 __device__ __forceinline__ double rotate_triple(const double *__restrict__ ent, int64_t E, int ld, int lane, int h, int t,
-                                                bool is_pos, const RowD<G, IT> &c, const RowD<G, IT> &s,
+                                                bool is_pos, double w, const RowD<G, IT> &c, const RowD<G, IT> &s,
                                                 const oea_rotate_cfg &cfg, const RotWs &ws, RowD<G, IT> &gth,
                                                 FamilyAcc<G, IT> &fam) {
     RowD<G, IT> rh, ih, rt, it_;
@@ -135,7 +139,7 @@ __device__ __forceinline__ double rotate_triple(const double *__restrict__ ent, 
     }
     dist = group_sum_d<G>(dist);
     const double x = is_pos ? dist - cfg.gamma : cfg.gamma - dist;
-    const double coef = is_pos ? sigmoid_(x) : -sigmoid_(x);          // d loss / d dist
+    const double coef = (is_pos ? sigmoid_(x) : -sigmoid_(x)) * w;    // d loss / d dist
     RowD<G, IT> g1, g2;
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -160,7 +164,7 @@ __device__ __forceinline__ double rotate_triple(const double *__restrict__ ent, 
         atomic_row<G, IT>(ws.ent_grad + (int64_t)t * ld, ld, lane, a);
         atomic_row<G, IT>(ws.ent_grad + (E + t) * ld, ld, lane, b);
     }
-    return softplus_(x);
+    return softplus_(x) * w;
 }
 
 template <int G, int IT>
@@ -178,6 +182,7 @@ __global__ __launch_bounds__(256) void rotate_triples(const double *__restrict__
     // step before, 12 M after -- not by the number of resident waves.)
     const int chunks = k > 0 ? (k + 1 + kChunk - 1) / kChunk : 1;
     const int64_t items = k > 0 ? n_pos * chunks : n_pos + n_neg;
+    const double neg_w = cfg.neg_loss_div > 1 ? 1.0 / (double)cfg.neg_loss_div : 1.0;
     double loss_local = 0.0;
     for (int64_t item = grp; item < items; item += ngrp) {
         const int64_t fam = k > 0 ? item / chunks : item;                 // the positive this group works for
@@ -198,14 +203,15 @@ __global__ __launch_bounds__(256) void rotate_triples(const double *__restrict__
         for (int j = j0; j < j1; ++j) {
             const int32_t *tr = j == 0 ? lead : neg + 3 * (fam * k + j - 1);
             const bool is_pos = j == 0 && !free_neg;
+            const double w = is_pos ? 1.0 : neg_w;
             if (tr[1] == r) {
-                l += rotate_triple<G, IT, ACC>(ent, E, ld, lane, tr[0], tr[2], is_pos, c, s, cfg, ws, gth, facc);
+                l += rotate_triple<G, IT, ACC>(ent, E, ld, lane, tr[0], tr[2], is_pos, w, c, s, cfg, ws, gth, facc);
             } else {                                    // not a corruption of this positive: its own relation row
                 RowD<G, IT> c2, s2, g2;
                 phase_row<G, IT>(rel, tr[1], ld, lane, cfg, c2, s2);
 #pragma unroll
                 for (int it = 0; it < IT; ++it) g2.v[it] = 0.0;
-                l += rotate_triple<G, IT, ACC>(ent, E, ld, lane, tr[0], tr[2], is_pos, c2, s2, cfg, ws, g2, facc);
+                l += rotate_triple<G, IT, ACC>(ent, E, ld, lane, tr[0], tr[2], is_pos, w, c2, s2, cfg, ws, g2, facc);
 #pragma unroll
                 for (int it = 0; it < IT; ++it) g2.v[it] *= cfg.phase_scale;
                 atomic_row<G, IT>(ws.rel_copy(item % kRelCopies) + (int64_t)tr[1] * ld, ld, lane, g2);
@@ -391,6 +397,7 @@ int oea_rotate_step(double *ent, double *ent_state, int64_t n_ent, double *rel, 
     OEA_REQUIRE(cfg->opt_kind >= OEA_OPT_SGD && cfg->opt_kind <= OEA_OPT_ADAM, "opt_kind");
     OEA_REQUIRE(cfg->opt_kind == OEA_OPT_SGD || (ent_state && rel_state), "Adagrad / Adam need their state arrays");
     OEA_REQUIRE(cfg->opt_kind != OEA_OPT_ADAM || cfg->t >= 1, "Adam: t >= 1");
+    OEA_REQUIRE(cfg->neg_loss_div >= 0, "neg_loss_div >= 0 (0 and 1: the negatives undivided)");
     RotWs ws;
     ws_layout(2 * n_ent, n_rel, ld, workspace, &ws);
     hipStream_t st = oea::as_stream(stream);

@@ -1,5 +1,5 @@
 // semantic_step.hip -- the training step of the semantic-matching models HolE (models/semantic/hole.py:41-86 of the
-// reference) and SimplE (models/semantic/simple.py:39-88).
+// reference), SimplE (models/semantic/simple.py:39-88) and DistMult (models/semantic/distmult.py:43-59).
 //
 //   HolE    u = l2n(ent)[e], rh = l2n(l2n(rel)[r]) (the relation row is normalised twice, hole.py:57),
 //           c[k] = sum_i uh[i] ut[(i + k) mod d] (circular correlation), score = -sigmoid(rh . c),
@@ -7,6 +7,9 @@
 //   SimplE  four tables stacked in two: ent rows [0, E) = H, [E, 2E) = T; rel rows [0, R) = R1, [R, 2R) = R2;
 //           score = (l2n(H[h] o R1[r]) . T[t] + l2n(H[t] o R2[r]) . T[h]) / 2 (each table row l2-normalised first),
 //           loss = sum_pos softplus(-score) + sum_neg softplus(score).
+//   DistMult u = l2n(ent)[e], w = l2n(rel)[r] (each by its flag), score = sum_d uh[d] w[d] ut[d],
+//           loss = MEAN over the N = n_pos + n_neg labelled triples of softplus(-y score), y = +1 positives, -1 negatives
+//           (batch.py:generate_triple_label_batch; the order of the labelled list does not enter the loss).
 //
 // One wave per positive and its k negatives; a lane holds columns 2 l and 2 l + 1 of every row.  The gradients w.r.t. the
 // (table-)normalised rows go into the step engine's scratch, entity rows and relation copy 0, and the engine's apply phase
@@ -47,6 +50,7 @@ struct SemArgs {
     grad_t *ent_grad, *rel_grad;
     flag_t *ent_touched, *rel_touched;
     double *loss_accum;
+    double inv_n;                 // DistMult: 1 / (n_pos + n_neg), the mean over the labelled triples
 };
 
 // columns 2 lane, 2 lane + 1 of a row (zero from dim on); ld % 4 == 0 keeps the float2 inside the row
@@ -313,6 +317,50 @@ __global__ __launch_bounds__(64 * kWaves) void simple_kernel(SemArgs A) {
     }
 }
 
+// ---- DistMult --------------------------------------------------------------------------------------------------------
+// s = sum_d uh w ut;  ds = dL/ds = -y sigmoid(-y s) / N;  dL/duh = ds (w o ut), dL/dw = ds (uh o ut), dL/dut = ds (uh o w).
+// With h == t both halves land in the same slot.
+__global__ __launch_bounds__(64 * kWaves) void distmult_kernel(SemArgs A) {
+    __shared__ __attribute__((aligned(16))) float buf[kWaves][kMaxDim];
+    __shared__ double wave_loss[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = A.k;
+    const float inv_n = (float)A.inv_n;
+    double loss_local = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * kWaves + wave; p < A.n_pos; p += (int64_t)gridDim.x * kWaves) {
+        const int32_t *tp = A.pos + 3 * p;
+        Slots<2> se;
+        Slots<1> sr;
+        se.set(0, tp[0]); se.set(1, tp[2]);
+        sr.set(0, tp[1]);
+        for (int q = 0; q <= k; ++q) {
+            const int32_t *tr = q == 0 ? tp : A.neg + 3 * (p * k + q - 1);
+            const int64_t h = tr[0], r = tr[1], t = tr[2];
+            const float2 a = load2(A.ent + h * A.ld, A.dim, lane), b = load2(A.ent + t * A.ld, A.dim, lane);
+            const float2 c = load2(A.rel + r * A.ld, A.dim, lane);
+            const float2 uh = scale2(a, inv_norm(a, A.ent_l2n)), ut = scale2(b, inv_norm(b, A.ent_l2n));
+            const float2 w = scale2(c, inv_norm(c, A.rel_l2n));
+            const float2 hw = mul2(uh, w);
+            const float score = dot2(hw, ut);
+            const float x = q == 0 ? -score : score;                            // -y s
+            loss_local += (double)softplus_f(x);
+            const float ds = (q == 0 ? -sigmoid_f(x) : sigmoid_f(x)) * inv_n;
+            se.add(h, scale2(mul2(w, ut), ds), A.ent_grad, A.ent_touched, A.ld, A.dim, lane, buf[wave]);
+            se.add(t, scale2(hw, ds), A.ent_grad, A.ent_touched, A.ld, A.dim, lane, buf[wave]);
+            sr.add(r, scale2(mul2(uh, ut), ds), A.rel_grad, A.rel_touched, A.ld, A.dim, lane, buf[wave]);
+        }
+        se.flush(A.ent_grad, A.ent_touched, A.ld, A.dim, lane, buf[wave]);
+        sr.flush(A.rel_grad, A.rel_touched, A.ld, A.dim, lane, buf[wave]);
+    }
+    if (lane == 0) wave_loss[wave] = loss_local;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < kWaves; ++w) s += wave_loss[w];
+        if (s != 0.0) atomicAdd(A.loss_accum, s * A.inv_n);
+    }
+}
+
 static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
@@ -322,7 +370,7 @@ extern "C" {
 int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
                       int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg,
                       const oea_step_cfg *cfg, void *step_workspace, double *loss_accum, void *stream) {
-    if (model != OEA_SEMANTIC_HOLE && model != OEA_SEMANTIC_SIMPLE) {
+    if (model != OEA_SEMANTIC_HOLE && model != OEA_SEMANTIC_SIMPLE && model != OEA_SEMANTIC_DISTMULT) {
         oea::set_error("oea_semantic_step: unknown model %d", model);
         return OEA_EUNSUPPORTED;
     }
@@ -371,8 +419,10 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
         A.ent_grad = static_cast<grad_t *>(eg); A.rel_grad = rel_grad;
         A.ent_touched = static_cast<flag_t *>(et); A.rel_touched = rel_touched;
         A.loss_accum = loss_accum;
+        A.inv_n = 1.0 / (double)(n_pos + n_neg);
         const unsigned grid = (unsigned)std::min<int64_t>(oea::ceil_div(n_pos, kWaves), kMaxBlocks);
         if (model == OEA_SEMANTIC_HOLE) hole_kernel<<<grid, 64 * kWaves, 0, st>>>(A);
+        else if (model == OEA_SEMANTIC_DISTMULT) distmult_kernel<<<grid, 64 * kWaves, 0, st>>>(A);
         else simple_kernel<<<grid, 64 * kWaves, 0, st>>>(A);
         OEA_CHECK_HIP(hipGetLastError());
     }

@@ -1,5 +1,5 @@
-"""The trainer of HolE and SimplE: one optimiser instance over the entity and relation tables (generate_optimizer,
-hole.py:85-86 / simple.py:86-88), stepped by oea_semantic_step (csrc/semantic_step.hip)."""
+"""The trainer of HolE, SimplE and DistMult: one optimiser instance over the entity and relation tables (generate_optimizer,
+hole.py:85-86 / simple.py:86-88 / distmult.py:59), stepped by oea_semantic_step (csrc/semantic_step.hip)."""
 import torch
 
 from ... import ops
@@ -12,7 +12,7 @@ class SemanticTrainer:
 
     def __init__(self, model, ent, rel, cfg, optimizer):
         if optimizer not in ('Adagrad', 'SGD'):
-            raise NotImplementedError("HolE / SimplE: optimizer=%s -- the semantic step trains with Adagrad (the shipped args "
+            raise NotImplementedError("HolE / SimplE / DistMult: optimizer=%s -- the semantic step trains with Adagrad (the shipped args "
                                       "files) or SGD" % optimizer)
         self.model, self.ent, self.rel, self.cfg = model, ent, rel, cfg
         dev = ent.var.device

@@ -149,11 +149,12 @@ def to_table64(array, dev=None):
 
 
 def make_rotate_cfg(gamma, dim, ent_l2_norm=True, rel_l2_norm=False, optimizer='Adam', lr=0.01, beta1=0.9, beta2=0.999,
-                    eps=1e-8, epsilon=2.0):
-    """bootea_rotate.py:29-33,90: embedding_range = (gamma + epsilon) / dim, phase = rel / (embedding_range / pi)."""
+                    eps=1e-8, epsilon=2.0, neg_loss_div=0):
+    """bootea_rotate.py:29-33,90: embedding_range = (gamma + epsilon) / dim, phase = rel / (embedding_range / pi).
+    neg_loss_div = k > 1: the negatives' half of the loss divided by k (the plain RotatE, rotate.py:81); 0 or 1: undivided."""
     rng = (float(gamma) + float(epsilon)) / dim
     return RotateCfg(float(gamma), 3.14159265358979323846 / rng, float(lr), float(beta1), float(beta2), float(eps), 0,
-                     int(bool(ent_l2_norm)), int(bool(rel_l2_norm)), OPT_KIND[optimizer], 0)
+                     int(bool(ent_l2_norm)), int(bool(rel_l2_norm)), OPT_KIND[optimizer], int(neg_loss_div))
 
 
 def rotate_workspace(n_ent, n_rel, ld, dev=None):
@@ -290,15 +291,15 @@ def transr_step(ent, ent_acc, rel, rel_acc, rel_matrix, rel_matrix_acc, dim, pos
                                 _p(workspace), _p(transr_ws), _p(loss_accum), _stream()))
 
 
-# ---- HolE / SimplE ----------------------------------------------------------------------------------------------
-SEMANTIC_HOLE, SEMANTIC_SIMPLE = 0, 1
+# ---- HolE / SimplE / DistMult -----------------------------------------------------------------------------------
+SEMANTIC_HOLE, SEMANTIC_SIMPLE, SEMANTIC_DISTMULT = 0, 1, 2
 SEMANTIC_MAX_DIM = 128
 
 
 def semantic_step(model, ent, ent_acc, rel, rel_acc, dim, pos, neg, cfg, workspace, loss_accum):
-    """One HolE / SimplE optimiser step in place (oea_semantic_step): model SEMANTIC_HOLE or SEMANTIC_SIMPLE (stacked tables:
-    ent = [H; T], rel = [R1; R2]); neg [n * k, 3] with neg[p*k:(p+1)*k] the corruptions of pos p, k = cfg.neg_group_k; the
-    batch loss is added to `loss_accum`."""
+    """One HolE / SimplE / DistMult optimiser step in place (oea_semantic_step): model SEMANTIC_HOLE, SEMANTIC_SIMPLE (stacked
+    tables: ent = [H; T], rel = [R1; R2]) or SEMANTIC_DISTMULT; neg [n * k, 3] with neg[p*k:(p+1)*k] the corruptions of pos p,
+    k = cfg.neg_group_k; the batch loss (DistMult: the mean over the n * (k + 1) labelled triples) is added to `loss_accum`."""
     n_neg = 0 if neg is None else neg.shape[0]
     check(lib().oea_semantic_step(int(model), _p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim,
                                   ent.shape[1], _p(pos), pos.shape[0], _p(neg), n_neg, C.byref(cfg), _p(workspace),

@@ -1,6 +1,6 @@
 """Hyper-parameter sets of the approaches on the hot path, as python dicts.
 
-The values are the ones the reference ships in run/args/{mtranse,bootea,aligne,gcnalign,transh,transd,hole,simple,iptranse,proje,...}_args_{15K,100K}.json
+The values are the ones the reference ships in run/args/{mtranse,bootea,aligne,gcnalign,transh,transd,hole,simple,rotate,iptranse,proje,...}_args_{15K,100K}.json
 (the `args_*` API: one attribute per key).  ``get_args(name, scale)`` returns an ``ARGs`` object that any
 model accepts through ``set_args``; a reference JSON file loaded with ``load_args`` works the same way.
 """
@@ -45,6 +45,14 @@ _ARGS = {
     "SimplE": dict(embedding_module="SimplE", alignment_module="sharing", dim=100, init="xavier", ent_l2_norm=True,
                    rel_l2_norm=True, neg_sampling="uniform", neg_triple_num=1, learning_rate=0.01, optimizer="Adagrad",
                    batch_size=5000, start_valid=10, eval_metric="inner", eval_norm=True),
+    # run/args/rotate_args_15K.json
+    "RotatE": dict(embedding_module="RotatE", alignment_module="sharing", dim=100, init="uniform", ent_l2_norm=True,
+                   rel_l2_norm=True, neg_sampling="uniform", neg_triple_num=10, gamma=12.0, learning_rate=0.1, optimizer="Adam",
+                   batch_size=5000, test_threads_num=2, start_valid=200, eval_metric="inner", eval_norm=True),
+    # ours, not the reference's (it ships no args file for DistMult): SimplE's set, the sibling loss
+    "DistMult": dict(embedding_module="DistMult", alignment_module="sharing", dim=100, init="xavier", ent_l2_norm=True,
+                     rel_l2_norm=True, neg_sampling="uniform", neg_triple_num=1, learning_rate=0.01, optimizer="Adagrad",
+                     batch_size=5000, start_valid=10, eval_metric="inner", eval_norm=True),
     # run/args/sea_args_15K.json
     "SEA": dict(embedding_module="SEA", alignment_module="mapping", dim=100, init="normal", ent_l2_norm=True, rel_l2_norm=True,
                 loss_norm="L2", margin=1.5, loss="margin-based", alpha_1=2.5, alpha_2=0.25, neg_sampling="uniform",
@@ -85,6 +93,8 @@ _SCALE_100K = {
     "TransD": dict(batch_size=20000),
     "HolE": dict(batch_size=20000),
     "SimplE": dict(batch_size=20000, start_valid=50),
+    "RotatE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=1),
+    "DistMult": dict(batch_size=20000, start_valid=50),            # ours: SimplE's changes
     "SEA": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
     "IPTransE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
     "ProjE": dict(batch_size=5000, batch_threads_num=3, test_threads_num=10, start_valid=300),

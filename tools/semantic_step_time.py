@@ -1,4 +1,4 @@
-"""Time of one HolE / SimplE training step (oea_semantic_step) at the EN-FR-15K-V1 and EN-FR-100K-V1 shapes, next to the
+"""Time of one HolE / SimplE / DistMult training step (oea_semantic_step) at the EN-FR-15K-V1 and EN-FR-100K-V1 shapes, next to the
 reference's formulation composed in torch (HolE: complex64 torch.fft; both: whole-table l2_normalize every step as TF does,
 autograd, Adagrad) -- the comparison leg, never the product path.
 
@@ -6,7 +6,7 @@ autograd, Adagrad) -- the comparison leg, never the product path.
 
 Workload per shape: a synthetic KG pair of that shape (modules/load/synth.py, ids shared as in alignment_module 'sharing'),
 batches of positives drawn from both KGs' triples (5,000 at 15K, 20,000 at 100K: the shipped args files), one uniform
-corruption of head or tail per positive, Adagrad, HolE margin 0.2.  Device timing: HIP events around `steps` consecutive
+corruption of head or tail per positive, Adagrad, HolE margin 0.2 (DistMult: the mean over the 2 B labelled triples).  Device timing: HIP events around `steps` consecutive
 steps after `warmup` steps.  Prints one JSON line per (model, shape)."""
 import argparse
 import json
@@ -45,6 +45,17 @@ def simple_torch_loss(tv, p, n):
     return torch.nn.functional.softplus(-score(p)).sum() + torch.nn.functional.softplus(score(n)).sum()
 
 
+def distmult_torch_loss(tv, p, n):
+    e, w = l2n(tv[0]), l2n(tv[1])
+    tr = torch.cat([p, n])
+    label = torch.cat([torch.ones(len(p), device=p.device), -torch.ones(len(n), device=p.device)])
+    return torch.nn.functional.softplus(-label * (e[tr[:, 0]] * w[tr[:, 1]] * e[tr[:, 2]]).sum(1)).mean()
+
+
+KINDS = {"HolE": "SEMANTIC_HOLE", "SimplE": "SEMANTIC_SIMPLE", "DistMult": "SEMANTIC_DISTMULT"}
+TORCH_LOSS = {"HolE": hole_torch_loss, "SimplE": simple_torch_loss, "DistMult": distmult_torch_loss}
+
+
 def run(model, shape, a):
     from openea_amd import ops
     from openea_amd.modules.base.initializers import xavier_host
@@ -62,7 +73,7 @@ def run(model, shape, a):
     bi, ri = np.meshgrid(np.arange(n_batches), np.arange(B), indexing="ij")
     neg[bi, ri, side] = rng.randint(0, E, (n_batches, B))
     pos_d, neg_d = ops.to_ids(pos, dev), ops.to_ids(neg, dev)
-    n_tab = 1 if model == "HolE" else 2
+    n_tab = 2 if model == "SimplE" else 1
     hosts = [xavier_host(rng, (E, d)) for _ in range(n_tab)] + [xavier_host(rng, (R, d)) for _ in range(n_tab)]
 
     # ---- device step ------------------------------------------------------------------------------------------------------
@@ -72,7 +83,7 @@ def run(model, shape, a):
     cfg = ops.make_step_cfg(loss="margin-based", margin=0.2, optimizer="Adagrad", lr=0.01, neg_group_k=1)
     ws = ops.step_workspace(ent.shape[0], rel.shape[0], ent.shape[1], dev)
     loss = torch.zeros(1, dtype=torch.float64, device=dev)
-    kind = ops.SEMANTIC_HOLE if model == "HolE" else ops.SEMANTIC_SIMPLE
+    kind = getattr(ops, KINDS[model])
 
     def dev_step(s):
         ops.semantic_step(kind, ent, accs[0], rel, accs[1], d, pos_d[s], neg_d[s], cfg, ws, loss)
@@ -90,7 +101,7 @@ def run(model, shape, a):
     # ---- comparison leg: the reference's formulation composed in torch ---------------------------------------------------
     tv = [torch.from_numpy(x.astype(np.float32)).to(dev).requires_grad_(True) for x in hosts]
     tacc = [torch.full_like(v, 0.1) for v in tv]
-    torch_loss = hole_torch_loss if model == "HolE" else simple_torch_loss
+    torch_loss = TORCH_LOSS[model]
 
     def torch_step(s):
         lv = torch_loss(tv, pos_d[s].long(), neg_d[s].long())
@@ -129,7 +140,7 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--torch-steps", type=int, default=10)
     ap.add_argument("--shapes", default="15K,100K")
-    ap.add_argument("--models", default="HolE,SimplE")
+    ap.add_argument("--models", default="HolE,SimplE,DistMult")
     ap.add_argument("--out", default=None, help="also write the results as a JSON list here")
     a = ap.parse_args()
     out = [run(m, s, a) for s in a.shapes.split(",") for m in a.models.split(",")]
