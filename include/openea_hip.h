@@ -653,10 +653,12 @@ size_t oea_topk_workspace_bytes(int64_t nq, int64_t nc);
 /* queries == candidates (q == c, the truncated-sampling refresh of one KG's entities against themselves): with a
  * workspace of this many bytes (0: shape not covered) oea_topk_inner computes only the tiles on and above the diagonal of
  * S = E E^T and feeds rows and columns from them (bit-identical result: S_ij == S_ji in the k-ordered fmaf chain).
- * Round 4: that sweep multiplies the bf16 hi / lo split of the rows (approximate survivors, the neighbourhood of the k-th value
+ * That sweep multiplies the bf16 hi / lo split of the rows (approximate survivors, the neighbourhood of the k-th value
  * decided by exact chains: the same neighbour sets) and collects the survivors in per-wave record streams that a second kernel
- * deals to per-row lists; OEA_TOPK_BF16=0 / OEA_TOPK_STREAM=0 (read once per process) select the fp32 sweep / the per-row
- * segment lists of round 3. */
+ * deals to per-row lists.  Covered: 12,288 (OEA_TOPK_SYM_MIN) <= n <= 131,072 rows (1,024 tiles of 128), k / n up to a few
+ * per cent.  Where the answer is 0 -- also under OEA_TOPK_BF16=0 (read once per process), and for 131,073..143,232 rows, which
+ * per-row segment lists served until they were retired -- oea_topk_inner computes the full N x N sweep on the general list
+ * path (nc >= 32,768) or the strips: the same neighbour sets; speed in that band not measured on either path. */
 size_t oea_topk_sym_workspace_bytes(int64_t n, int32_t k);
 int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int64_t nc, int32_t ldc,
                    int32_t dim, int32_t k, const int32_t *id_map, int32_t *out_idx, void *workspace,

@@ -958,111 +958,13 @@ __global__ __launch_bounds__(256, 2) void topk_append_kernel(
         if (qi[tn] < nq) counts[qi[tn] * nseg + sidx] = (int32_t)((boff[tn] - bbeg[tn]) >> 2);
 }
 
-// ---- symmetric neighbour search: queries == candidates, S = E E^T ---------------------------------------------------------
-// Only the tiles on and above the diagonal are computed (bitwise S_ij == S_ji: the k-ordered fmaf chain multiplies the same
-// pairs in the same order).  A work item = (query tile qt, candidate tiles [ct_begin, ct_end) with ct_begin >= qt); its tiles
-// feed TWO sets of lists: the query side as in topk_append_kernel (lane-private segments of the rows of tile qt), and -- off
-// the diagonal -- the CANDIDATE side: row j of tile ct receives (S_ji, i) for the rows i of tile qt at or above thr[j].
-// Candidate-side entries go to one small segment per (row j, query tile qt, wave column wn): the 32 lanes of a half-wave
-// hold the SAME candidate j for 32 different queries, so the slots of an MFMA register's survivors are the prefix counts of
-// a wave ballot -- no atomics, no LDS, no barrier; the segment is written by this wave only, its length goes to
-// ccounts[(j * T + qt) * 2 + wn] (uint8).  (First version: one segment per (j, qt), slots from an LDS counter per candidate,
-// a returning LDS atomic per survivor between two barriers: 17.0 ms for the 100,000^2 sweep.)
-// BF16: e = the hi / lo split rows (pack_rows_bf16_kernel), the values appended are v~ with |v~ - v| <= *tol_ptr, and the cut is
-// thr - tol: every pair whose EXACT value reaches thr is in the lists (the select resolves the neighbourhood of the k-th
-// value with exact chains, list_select_kernel).
-template <bool BF16>
-__global__ __launch_bounds__(256, 2) void topk_append_sym_kernel(
-    const float *__restrict__ e, int64_t n, int ld, int dim, const float *__restrict__ thr, const int4 *__restrict__ items,
-    int nseg, int cap, float *__restrict__ list_vals, int32_t *__restrict__ list_cols, int32_t *__restrict__ counts, int T, int ccap,
-    uint2 *__restrict__ clists, uint8_t *__restrict__ ccounts, int32_t *__restrict__ spill_cnt, uint2 *__restrict__ spill, int sp_cap,
-    const float *__restrict__ tol_ptr) {
-    __shared__ __attribute__((aligned(16))) float As[2 * TILE * LDS_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[2 * TILE * LDS_LD];
-    const int4 item = items[blockIdx.x];                           // (qt, ct_begin, ct_end, segment group)
-    const int qt = item.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int half = lane >> 5, l32 = lane & 31;
-    const int64_t q0 = (int64_t)qt * TILE;
-    const int sidx = (item.w * 2 + wm) * 2 + half;
-    const float tol = BF16 ? *tol_ptr : 0.f;
-    float th[2];
-    uint32_t boff[2], bbeg[2], blast[2];
-    int64_t qi[2];
-    char *__restrict__ vbase = reinterpret_cast<char *>(list_vals + q0 * nseg * (int64_t)cap);
-    char *__restrict__ cbase = reinterpret_cast<char *>(list_cols + q0 * nseg * (int64_t)cap);
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) {
-        const int ql = wn * 64 + tn * 32 + l32;
-        qi[tn] = q0 + ql;
-        th[tn] = qi[tn] < n ? thr[qi[tn]] - tol : INFINITY;
-        bbeg[tn] = boff[tn] = 4u * (uint32_t)((ql * nseg + sidx) * cap);
-        blast[tn] = boff[tn] + 4u * (uint32_t)(cap - 1);
-    }
-    // the candidate of accumulator register (tm, r) in this half-wave: local row jl0 + tm * 32 + (r & 3) + 8 * (r >> 2);
-    // lane l32 = tm * 16 + r looks after that candidate's threshold and segment length
-    const int jl0 = wm * 64 + 4 * half;
-    const int my_jl = jl0 + (l32 >> 4) * 32 + (l32 & 3) + 8 * ((l32 & 15) >> 2);
-    const uint32_t below = (1u << l32) - 1u;
-    auto epilogue = [&](int64_t t, f32x16 (&acc)[2][2]) {
-            const int ct = item.y + (int)t;
-            const int64_t c0 = (int64_t)ct * TILE;
-            const bool offdiag = ct != qt;                           // workgroup-uniform
-            const int64_t my_j = c0 + my_jl;
-            const float my_tc = (offdiag && my_j < n) ? thr[my_j] - tol : INFINITY;
-            int my_cnt = 0;
-#pragma unroll
-            for (int tm = 0; tm < 2; ++tm) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int jl = jl0 + tm * 32 + (r & 3) + 8 * (r >> 2);
-                    const int j = (int)c0 + jl;
-                    const bool jin = j < n;
-                    const float tc = __shfl(my_tc, (lane & 32) + tm * 16 + r, 64);
-                    uint2 *__restrict__ seg = clists + (((int64_t)j * T + qt) * 2 + wn) * ccap;
-                    int cnt = 0;
-#pragma unroll
-                    for (int tn = 0; tn < 2; ++tn) {
-                        const float v = acc[tm][tn][r];
-                        if (v >= th[tn] && jin) {
-                            const uint32_t at = min(boff[tn], blast[tn]);           // last slot = scratch, see topk_append_kernel
-                            *reinterpret_cast<float *>(vbase + at) = v;
-                            *reinterpret_cast<int32_t *>(cbase + at) = j;
-                            if (boff[tn] >= blast[tn]) {
-                                const int pos = atomicAdd(spill_cnt + qi[tn], 1);
-                                if (pos < sp_cap) spill[qi[tn] * sp_cap + pos] = make_uint2(__float_as_uint(v), (uint32_t)j);
-                            }
-                            boff[tn] += 4u;
-                        }
-                        const bool pc = v >= tc && qi[tn] < n;       // tc = +inf on the diagonal and past the last row
-                        const unsigned long long bal = __ballot(pc);
-                        const uint32_t bh = half ? (uint32_t)(bal >> 32) : (uint32_t)bal;
-                        const int slot = cnt + __popc(bh & below);
-                        if (pc) seg[min(slot, ccap - 1)] = make_uint2(__float_as_uint(v), (uint32_t)qi[tn]);
-                        if (pc && slot >= ccap - 1) {                 // last slot = scratch; row j's spill list
-                            const int pos = atomicAdd(spill_cnt + j, 1);
-                            if (pos < sp_cap) spill[(int64_t)j * sp_cap + pos] = make_uint2(__float_as_uint(v), (uint32_t)qi[tn]);
-                        }
-                        cnt += __popc(bh);
-                    }
-                    if (l32 == tm * 16 + r) my_cnt = cnt;
-                }
-            }
-            // lengths saturate at 255; the select reads min(length, ccap - 1) entries, the rest sits in the row's spill list
-            if (offdiag && my_j < n) ccounts[(my_j * T + qt) * 2 + wn] = (uint8_t)min(my_cnt, 255);
-        };
-    auto m_tile = [=](int64_t t) { return (int64_t)(item.y + t) * TILE; };
-    if constexpr (BF16) tile_pipeline_bf16<false>(e, ld, e, dim, q0, (int64_t)(item.z - item.y), m_tile, As, Bs, epilogue);
-    else tile_pipeline_packed(e, ld, e, dim, q0, (int64_t)(item.z - item.y), m_tile, As, Bs, epilogue);
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-        if (qi[tn] < n) counts[qi[tn] * nseg + sidx] = (int32_t)((boff[tn] - bbeg[tn]) >> 2);
-}
-
 // ---- stream form of the symmetric neighbour sweep (round 4) ------------------------------------------------------------------
-// The append kernel above gives every (query, segment) and every (candidate, query tile) its own little list: 4-byte stores to
-// ~64 different lines per instruction and ~28 vector instructions per accumulator element.  Here every WAVE owns two
+// queries == candidates, S = E E^T: only the tiles on and above the diagonal are computed (bitwise S_ij == S_ji: the k-ordered
+// chain multiplies the same pairs in the same order).  A work item = (query tile qt, candidate tiles [ct_begin, ct_end) with
+// ct_begin >= qt); its tiles feed BOTH sides: the rows of tile qt, and -- off the diagonal -- row j of tile ct, which receives
+// (S_ji, i) for the rows i of tile qt.  e = the bf16 hi / lo split rows (pack_rows_bf16_kernel): the values recorded are v~ with
+// |v~ - v| <= *tol_ptr and the cut is thr - tol, so every pair whose EXACT value reaches thr is recorded (the select resolves
+// the neighbourhood of the k-th value with exact chains, list_select_kernel).  Every WAVE owns two
 // append-only streams of 8-byte records (value bits, tag): survivors of the query side (v~ >= cut of the query; tag = local
 // query row << 24 | candidate) and of the candidate side (v~ >= cut of the candidate; tag = local candidate row << 24 |
 // query), slots = stream position + prefix of a ballot -- full-line stores, no per-lane bookkeeping.  The candidate stream's
@@ -1075,7 +977,7 @@ __global__ __launch_bounds__(256, 2) void topk_append_sym_kernel(
 // shared pool with one atomic per chunk; topk_overflow_kernel (topk.hip) appends them to the compact lists after the bucketing.
 // (Handling the overflow inside the sweep -- a second pass over the accumulators -- cost the sweep 1.2 ms of spills and code size
 // on tables that never overflow.)  Only a pool or redo list that runs dry marks rows as lost (row_fail): strip fallback.
-constexpr int kOvfChunk = 512;                       // records per overflow chunk
+using oea::kOvfChunk;                                // records per overflow chunk (common.h)
 
 struct OvfState {                                    // per wave (wave-uniform)
     uint4 *__restrict__ pool;
@@ -1132,48 +1034,15 @@ __device__ __forceinline__ void stream_ovf_tile(const f32x16 (&acc)[2][2], int c
     }
 }
 
-template <bool INTERIOR>
-__device__ __forceinline__ void stream_tile(const f32x16 (&acc)[2][2], int c0, int jl0, int n, const float (&th)[2], const uint32_t (&rtag)[2],
-                                            const uint32_t (&qidx)[2], float my_tc, int lane, char *__restrict__ rs, uint32_t rbytes,
-                                            char *__restrict__ cs, uint32_t cbytes, uint32_t &rpos, uint32_t &cpos) {
-    // positions and capacities in BYTES (32-bit offsets from wave-uniform bases: one shift per record, no 64-bit address math)
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jl = jl0 + tm * 32 + (r & 3) + 8 * (r >> 2);
-            const int j = c0 + jl;
-            const float tc = __shfl(my_tc, (lane & 32) + tm * 16 + r, 64);
-            const uint32_t ctag = (uint32_t)jl << 24;
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
-                const float v = acc[tm][tn][r];
-                const bool pr = INTERIOR ? v >= th[tn] : (v >= th[tn] && j < n);
-                unsigned long long m = __ballot(pr);
-                if (pr) {
-                    const uint32_t at = rpos + 8u * __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (at < rbytes) *reinterpret_cast<uint2 *>(rs + at) = make_uint2(__float_as_uint(v), rtag[tn] | (uint32_t)j);
-                }
-                rpos += 8u * (uint32_t)__popcll(m);
-                const bool pc = v >= tc;                          // tc = +inf on the diagonal, past the last row; th-side rows past n never match
-                m = __ballot(pc);
-                if (pc) {
-                    const uint32_t at = cpos + 8u * __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (at < cbytes) *reinterpret_cast<uint2 *>(cs + at) = make_uint2(__float_as_uint(v), ctag | qidx[tn]);
-                }
-                cpos += 8u * (uint32_t)__popcll(m);
-            }
-        }
-    }
-}
-
-// ---- the same records without a branch per accumulator (round 6) --------------------------------------------------------------------
-// stream_tile's `if (pr)` is taken for 4 of 5 accumulators (k / n = 2 %: some lane of the 64 passes), each time through
-// s_and_saveexec / s_cbranch / 64-bit address arithmetic / a second compare against the capacity: ~190 cycles per accumulator and
-// side when nothing overlaps it (measured with one wave per SIMD: 24 K cycles of epilogue beside 3 K of MFMA per tile).  Here one
-// accumulator and side is ONE straight block: v_cmpx puts the predicate into EXEC, the slot is mbcnt(EXEC), the record leaves through
-// a raw buffer whose num_records IS the stream's capacity (the hardware drops what does not fit: positions, and so the redo pass,
-// are unchanged), the position advances on the scalar unit, EXEC is restored.  5 VALU + 2 stores + 3 SALU, no branch.
+// ---- the record epilogue: no branch per accumulator (round 6) -------------------------------------------------------------------------
+// Positions and capacities are in BYTES (32-bit offsets from wave-uniform bases).  A first version branched per accumulator and side
+// (`if (pr)`: taken for 4 of 5 accumulators at k / n = 2 %, some lane of the 64 passes), each time through s_and_saveexec /
+// s_cbranch / 64-bit address arithmetic / a second compare against the capacity: ~190 cycles per accumulator and side when nothing
+// overlaps it (measured with one wave per SIMD: 24 K cycles of epilogue beside 3 K of MFMA per tile; 13.4 against 11.6 ms per
+// 100,000^2 search, and the register-operand sweep spilled with it).  Here one accumulator and side is ONE straight block: v_cmpx
+// puts the predicate into EXEC, the slot is mbcnt(EXEC), the record leaves through a raw buffer whose num_records IS the stream's
+// capacity (the hardware drops what does not fit: positions, and so the redo pass, are unchanged), the position advances on the
+// scalar unit, EXEC is restored.  5 VALU + 2 stores + 3 SALU, no branch.
 template <uint32_t TAG_ADD>
 __device__ __forceinline__ void stream_append(float v, float cut, uint32_t tag_base, __amdgpu_buffer_rsrc_t srd, uint32_t &pos,
                                               unsigned long long full) {
@@ -1225,13 +1094,12 @@ __device__ __forceinline__ void stream_tile_fast(const f32x16 (&acc)[2][2], cons
 }
 
 // NCH = Kp / 32 in {1..4}: the query tile's operand in registers (tile_pipeline_bf16_breg); 0: both operands through LDS
-// FAST: every tile through stream_tile_fast (compile-time: the branching epilogue and its registers are not in the kernel)
-template <int NCH, bool FAST = false>
+template <int NCH>
 __global__ __launch_bounds__(256, 2) void topk_stream_sym_kernel(
     const float *__restrict__ e, int64_t n, int kp, int dim, const float *__restrict__ thr, const int4 *__restrict__ items,
     uint2 *__restrict__ row_streams, int rcap, uint2 *__restrict__ col_streams, int ccap, int32_t *__restrict__ row_cnt,
     int32_t *__restrict__ col_off, int lp1, uint8_t *__restrict__ row_fail, const float *__restrict__ tol_ptr,
-    int32_t *__restrict__ redo_cnt, int4 *__restrict__ redo, int redo_cap, int fast) {
+    int32_t *__restrict__ redo_cnt, int4 *__restrict__ redo, int redo_cap) {
     __shared__ __attribute__((aligned(16))) float lds[NCH > 0 ? 4 * TILE * PLD : 4 * TILE * LDS_LD];
     float *As = lds, *Bs = lds + 2 * TILE * LDS_LD;
     const int4 item = items[blockIdx.x];                           // (qt, ct_begin, ct_end, segment group)
@@ -1271,7 +1139,6 @@ __global__ __launch_bounds__(256, 2) void topk_stream_sym_kernel(
     const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(rs), 0, (int)rbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(cs), 0, (int)cbytes, 0x00020000);
     const uint32_t cq[2] = {((uint32_t)jl0 << 24) | qidx[0], ((uint32_t)jl0 << 24) | qidx[1]};
-    const bool fast_on = fast != 0;
     float thr_pre = INFINITY;                                        // thr of this lane's candidate row in the tile about to be finished
     {
         const int64_t j0 = (int64_t)item.y * TILE + my_jl;
@@ -1300,18 +1167,15 @@ __global__ __launch_bounds__(256, 2) void topk_stream_sym_kernel(
                         if (qi[tn] >= n) acc[tm][tn][r] = -INFINITY;
         }
         const uint32_t r0 = rpos, p0 = cpos;
-        if (FAST || (c0 + TILE <= n && fast_on)) {
-            if (FAST && c0 + TILE > n) {                             // ragged last candidate tile: rows past n never pass a cut
+        if (c0 + TILE > n) {                                         // ragged last candidate tile: rows past n never pass a cut
 #pragma unroll
-                for (int tm = 0; tm < 2; ++tm)
+            for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        if ((int)c0 + jl0 + tm * 32 + (r & 3) + 8 * (r >> 2) >= (int)n) { acc[tm][0][r] = -INFINITY; acc[tm][1][r] = -INFINITY; }
-            }
-            const uint32_t rj[2] = {rtag[0] + (uint32_t)((int)c0 + jl0), rtag[1] + (uint32_t)((int)c0 + jl0)};
-            stream_tile_fast(acc, th, rj, cq, my_tc, lane, srd_r, srd_c, rpos, cpos);
-        } else if (c0 + TILE <= n) stream_tile<true>(acc, (int)c0, jl0, (int)n, th, rtag, qidx, my_tc, lane, rs, rbytes, cs, cbytes, rpos, cpos);
-        else stream_tile<false>(acc, (int)c0, jl0, (int)n, th, rtag, qidx, my_tc, lane, rs, rbytes, cs, cbytes, rpos, cpos);
+                for (int r = 0; r < 16; ++r)
+                    if ((int)c0 + jl0 + tm * 32 + (r & 3) + 8 * (r >> 2) >= (int)n) { acc[tm][0][r] = -INFINITY; acc[tm][1][r] = -INFINITY; }
+        }
+        const uint32_t rj[2] = {rtag[0] + (uint32_t)((int)c0 + jl0), rtag[1] + (uint32_t)((int)c0 + jl0)};
+        stream_tile_fast(acc, th, rj, cq, my_tc, lane, srd_r, srd_c, rpos, cpos);
         if (rpos > rbytes || cpos > cbytes) {                        // wave-uniform, rare: records of this tile did not fit
             int slot = 0;
             if (lane == 0) {
@@ -3234,14 +3098,6 @@ int topk_append_chunks(int64_t nq, int64_t nc) {
     int tpc;
     return pick_chunks(ceil_div(nq, TILE), ceil_div(nc, TILE), &tpc);
 }
-void topk_append_sym_packed(const float *ep, int64_t n, int kp, int dim, const float *thr, const void *items, int n_items, int nseg,
-                            int cap, float *list_vals, int32_t *list_cols, int32_t *counts, int T, int ccap, void *clists,
-                            uint8_t *ccounts, int32_t *spill_cnt, void *spill, int sp_cap, hipStream_t st) {
-    topk_append_sym_kernel<false><<<(unsigned)n_items, 256, 0, st>>>(ep, n, kp, dim, thr, static_cast<const int4 *>(items), nseg,
-                                                                     cap, list_vals, list_cols, counts, T, ccap,
-                                                                     static_cast<uint2 *>(clists), ccounts, spill_cnt,
-                                                                     static_cast<uint2 *>(spill), sp_cap, nullptr);
-}
 // stream form (topk_stream_sym_kernel): rows split and packed into slot 3, the bound into tol_dev[0], one launch
 int topk_stream_sym_bf16(const float *src, int64_t n, int ld, int dim, const float *thr, const void *items, int n_items, void *row_streams,
                          int rcap, void *col_streams, int ccap, int32_t *row_cnt, int32_t *col_off, int lp1, uint8_t *row_fail,
@@ -3255,42 +3111,22 @@ int topk_stream_sym_bf16(const float *src, int64_t n, int ld, int dim, const flo
     row_norm_max_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(src, n, ld, dim, reinterpret_cast<unsigned *>(tol_dev) + 1);
     knn_tol_kernel<<<1, 1, 0, st>>>(tol_dev, bf16_eps_rel(dim, false));
     static const int nch_env = [] { const char *e = getenv("OEA_TOPK_STREAM_NCH"); return e ? atoi(e) : 1; }();
-    // OEA_TOPK_STREAM_FAST=0: the branching epilogue (stream_tile) on every tile -- the ablation of stream_tile_fast
-    static const int fast_env = [] { const char *e = getenv("OEA_TOPK_STREAM_FAST"); return (e && e[0] == '0') ? 0 : 1; }();
-#define OEA_STREAM_LAUNCH(N, F)                                                                                                       \
-    topk_stream_sym_kernel<N, F><<<(unsigned)n_items, 256, 0, st>>>(op.p, n, op.kp, dim, thr, static_cast<const int4 *>(items),         \
+#define OEA_STREAM_LAUNCH(N)                                                                                                          \
+    topk_stream_sym_kernel<N><<<(unsigned)n_items, 256, 0, st>>>(op.p, n, op.kp, dim, thr, static_cast<const int4 *>(items),            \
                                                                  static_cast<uint2 *>(row_streams), rcap, static_cast<uint2 *>(col_streams), \
                                                                  ccap, row_cnt, col_off, lp1, row_fail, tol_dev, redo_cnt,              \
-                                                                 static_cast<int4 *>(redo), redo_cap, fast_env)
+                                                                 static_cast<int4 *>(redo), redo_cap)
     // the query operand in registers (tile_pipeline_bf16_breg: the candidate stages alone travel through LDS, nothing is re-sent per chunk)
-    // for 64 < dim <= 128 when the branch-free epilogue is compiled in alone: with the branching one the kernel spilled (13.3 -> 20.8 ms),
-    // without it it fits (20 B of scratch) -- 11.3 -> 10.5 ms at 100,000^2 x 100.  OEA_TOPK_STREAM_NCH=0: both operands through LDS
-    const bool breg = nch_env != 0 && fast_env;
-    if (breg && op.kp == 128) OEA_STREAM_LAUNCH(4, true);
-    else if (breg && op.kp == 96) OEA_STREAM_LAUNCH(3, true);
-    else if (fast_env) OEA_STREAM_LAUNCH(0, true);
-    else OEA_STREAM_LAUNCH(0, false);
+    // for 64 < dim <= 128: the kernel fits (20 B of scratch) -- 11.3 -> 10.5 ms at 100,000^2 x 100.  OEA_TOPK_STREAM_NCH=0: both operands
+    // through LDS
+    const bool breg = nch_env != 0;
+    if (breg && op.kp == 128) OEA_STREAM_LAUNCH(4);
+    else if (breg && op.kp == 96) OEA_STREAM_LAUNCH(3);
+    else OEA_STREAM_LAUNCH(0);
 #undef OEA_STREAM_LAUNCH
     topk_stream_redo_kernel<<<2048, 256, 0, st>>>(op.p, n, op.kp, dim, thr, static_cast<const int4 *>(items), rcap, ccap, row_fail, tol_dev,
                                                   redo_cnt, static_cast<const int4 *>(redo), redo_cap, static_cast<uint4 *>(ovf_pool), ovf_alloc,
                                                   ovf_len, ovf_chunks);
-    return OEA_OK;
-}
-// the same sweep on the hi / lo split rows of `src` (packed here into slot 3); tol_dev[0] receives the bound on |v~ - v|
-// (max row norm^2 x eps(dim), computed on the device) that the sweep cuts by and the select resolves with
-int topk_append_sym_bf16(const float *src, int64_t n, int ld, int dim, const float *thr, const void *items, int n_items, int nseg,
-                         int cap, float *list_vals, int32_t *list_cols, int32_t *counts, int T, int ccap, void *clists,
-                         uint8_t *ccounts, int32_t *spill_cnt, void *spill, int sp_cap, float *tol_dev, hipStream_t st) {
-    PackedOp op;
-    const int rc = pack_operand_bf16(3, src, n, ld, dim, st, &op);
-    if (rc != OEA_OK) return rc;
-    OEA_CHECK_HIP(hipMemsetAsync(tol_dev, 0, 8, st));
-    row_norm_max_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(src, n, ld, dim, reinterpret_cast<unsigned *>(tol_dev) + 1);
-    knn_tol_kernel<<<1, 1, 0, st>>>(tol_dev, bf16_eps_rel(dim, false));
-    topk_append_sym_kernel<true><<<(unsigned)n_items, 256, 0, st>>>(op.p, n, op.kp, dim, thr, static_cast<const int4 *>(items), nseg,
-                                                                          cap, list_vals, list_cols, counts, T, ccap,
-                                                                          static_cast<uint2 *>(clists), ccounts, spill_cnt,
-                                                                          static_cast<uint2 *>(spill), sp_cap, tol_dev);
     return OEA_OK;
 }
 void topk_append_packed(const float *qp, int64_t nq, const float *cp, int64_t nc, int kp, int dim, const float *thr, int cap,

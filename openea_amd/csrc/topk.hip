@@ -21,13 +21,13 @@
 //   oracle_topk_inner.
 //
 // Which path oea_topk_inner takes (all give the same result):
-//   queries == candidates, 12,288 <= N <= 131,072   stream form (round 4): sampled thresholds; upper-triangle tile sweep on the bf16
+//   queries == candidates, 12,288 <= N <= 131,072   stream form: sampled thresholds; upper-triangle tile sweep on the bf16
 //                                                   hi / lo split writing per-wave record streams (sim_rank.hip:
 //                                                   topk_stream_sym_kernel, redo list + overflow pool for crowded waves);
 //                                                   topk_bucket_kernel -> compact per-row lists; list_select_kernel (exact
 //                                                   chains around the k-th approximate value); strip fallback for failed rows
-//   queries == candidates, N >= 32,768, else        per-row segment lists from the symmetric sweep (round 3; bf16 or fp32 sweep)
-//   nc >= 32,768, nq >= 4,096                       per-query segment lists from the full sweep (fp32)
+//   nc >= 32,768, nq >= 4,096                       per-query segment lists from the full sweep (bf16 hi / lo split; OEA_TOPK_BF16=0:
+//                                                   fp32) -- also queries == candidates outside the stream form's range
 //   otherwise                                       N x N strips + per-row select (above)
 #include <math.h>
 #include <stdlib.h>
@@ -723,7 +723,7 @@ __global__ __launch_bounds__(SEL_THREADS) void row_select_sampled_kernel(const f
 constexpr int kSample = 2048;          // 2,048 sampled candidates: survivors ~ r N / S +- 1/sqrt(r) (r ~ 71 at k/N = 2 %)
 constexpr int kMaxSeg = 256;              // query-side segments per row
 constexpr int kSpillCap = 512;             // entries of a row's spill list (appends that found their segment full)
-constexpr int kMaxSegAll = 2304;          // + two candidate-side segments per query tile (symmetric search: T <= 1,100 tiles)
+constexpr int kMaxSegAll = kMaxSeg + 1;   // + the row's spill list: every segment list_select_kernel scans (sizes its registers and LDS)
 
 __device__ __forceinline__ float ord2f(uint32_t key) {
     return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
@@ -807,7 +807,7 @@ __global__ __launch_bounds__(256) void kth_value_kernel(const float *__restrict_
 }
 
 constexpr int kStreamMaxT = 1024;             // target tiles: <= 131,072 rows (the slice table is (64 + 4 T) * 8 B of LDS)
-constexpr int kOvfChunkRecs = 512;            // == kOvfChunk (sim_rank.hip)
+using oea::kOvfChunk;                         // records per chunk of the overflow pool (common.h)
 constexpr int kPerThread = 24;            // list entries a thread keeps in registers: lists of up to 6,144 survivors
 constexpr int kBitWords = 8192;           // bitmap of selected columns in (dynamic) LDS: nc <= 262,144
 
@@ -820,8 +820,7 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
                                                                    const float *__restrict__ thr, int nseg, int cap, int64_t nc,
                                                                    int k, const int32_t *__restrict__ id_map, int32_t *__restrict__ out,
                                                                    int32_t *__restrict__ fail_rows, int32_t *__restrict__ n_fail,
-                                                                   const uint2 *__restrict__ clists, const uint8_t *__restrict__ ccounts,
-                                                                   int T, int ccap, const int32_t *__restrict__ spill_cnt,
+                                                                   const int32_t *__restrict__ spill_cnt,
                                                                    const uint2 *__restrict__ spill, int stop_after,
                                                                    const float *__restrict__ exact_src, int ld_src, int dim,
                                                                    const float *__restrict__ tol_ptr,
@@ -838,7 +837,6 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
     // exact_q != NULL: the query rows of this launch come from another table than the candidates (row r of the launch = exact_q + r ld_q)
     // stop_after (experiments, OEA_TOPK_SELECT_STOP): leave after phase 1 (lengths + scan), 2 (gather), 3 (histogram + bucket),
     // 4 (threshold bucket ranked), 5 (bitmap set); 0 = run to the end.  Results are garbage when it is set.
-    // symmetric search (T > 0): T more segments per row, one per query tile, of (value, column) pairs (topk_append_sym_kernel)
     __shared__ int hist[kBins];
     // the segment offsets (lengths + scan, gather: phases 1-2) and the candidate tables (threshold bucket, band: phases 4-5) never live
     // at the same time (barriers in between): one array -- 8 KB less static LDS = FIVE workgroups per CU instead of four at nc = 100,000
@@ -856,9 +854,9 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
     if (tid == 0) { s_bad = 0; s_ncand = 0; s_nband = 0; }
     __syncthreads();
     const float tol = tol_ptr ? *tol_ptr : 0.f;
-    // segment lengths -> exclusive offsets (block scan: the symmetric search has hundreds of segments per row)
+    // segment lengths -> exclusive offsets (block scan: up to kMaxSeg segments per row)
     // + the row's spill list as the last segment (entries whose own segment was full)
-    const int nst = nseg + T + 1;
+    const int nst = nseg + 1;
     constexpr int kSegPer = (kMaxSegAll + SEL_THREADS - 1) / SEL_THREADS;
     int seg_c[kSegPer];
     int mine = 0;
@@ -874,8 +872,6 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
         int c = 0;
         if (sg < nseg) {
             c = min(counts[row * nseg + sg], cap - 1);             // the last slot of a segment is scratch (topk_append_kernel)
-        } else if (sg < nseg + T) {
-            c = min((int)ccounts[row * T + (sg - nseg)], ccap - 1);
         } else if (sg < nst) {
             c = spill_cnt[row];
             if (c > kSpillCap) s_bad = 1;                        // the spill list overflowed as well: strip path
@@ -895,7 +891,7 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
     const int words = (int)((nc + 31) / 32);
     for (int b = tid; b < kBins; b += SEL_THREADS) hist[b] = 0;
     // owner[i] = the segment of list position i, written by the thread that counted the segment: the gather below finds an
-    // entry with two LDS reads instead of a binary search over ~1,600 segment offsets (11 dependent reads per entry: the
+    // entry with two LDS reads instead of a binary search over the segment offsets (11 dependent reads per entry: the
     // gather was 2.3 ms of the select's 4.7 at 100,000 rows).  The table lives in the bitmap's storage, which is zeroed after
     // the gather.
     uint16_t *owner = reinterpret_cast<uint16_t *>(bitmap);
@@ -937,12 +933,8 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
                     const int64_t at = (int64_t)lo_s * cap + (i - s_off[lo_s]);
                     val[e] = vb[at];
                     col[e] = cb[at];
-                } else if (lo_s == nst - 1) {
-                    const uint2 pr = spill[row * kSpillCap + (i - s_off[lo_s])];
-                    val[e] = __uint_as_float(pr.x);
-                    col[e] = (int)pr.y;
                 } else {
-                    const uint2 pr = clists[((int64_t)row * T + (lo_s - nseg)) * ccap + (i - s_off[lo_s])];
+                    const uint2 pr = spill[row * kSpillCap + (i - s_off[lo_s])];
                     val[e] = __uint_as_float(pr.x);
                     col[e] = (int)pr.y;
                 }
@@ -1166,7 +1158,7 @@ static int select_stop() {
 static ListPlan plan_lists(int64_t nq, int64_t nc, int k, size_t ws_bytes) {
     ListPlan p;
     // OEA_TOPK_LISTS_MIN = 8192 / 16384 measured on random rows (gpurun_out r03q): 30,000^2 x 100, k = 600 2.84 vs 3.39 ms through
-    // strips, 15,000^2 even; not enabled: trained tables overflow the lists at these sizes (see plan_sym)
+    // strips, 15,000^2 even; not enabled: trained tables overflow the lists at these sizes
     static const int64_t min_nc = [] { const char *e = getenv("OEA_TOPK_LISTS_MIN"); return e ? (int64_t)atoll(e) : (int64_t)32768; }();
     if (nq < 4096 || nc < min_nc) return p;
     const double e = (double)k * kSample / (double)nc;
@@ -1214,66 +1206,6 @@ static ListPlan plan_lists(int64_t nq, int64_t nc, int k, size_t ws_bytes) {
 }
 
 // ---- symmetric search (queries == candidates): the tiles on and above the diagonal serve rows AND columns ---------------
-struct SymPlan {
-    bool ok = false;
-    int r = 0, T = 0, L = 0, groups = 0, nseg = 0, cap = 0, ccap = 0, n_items = 0;
-    int64_t stride = 0, ld = 0;
-    size_t off_thr = 0, off_counts = 0, off_ccounts = 0, off_fail = 0, off_nfail = 0, off_items = 0, off_vals = 0, off_cols = 0,
-           off_clists = 0, off_strip = 0, off_spcnt = 0, off_spill = 0, total = 0;
-};
-
-static SymPlan plan_sym(int64_t n, int k, size_t ws_bytes) {
-    SymPlan p;
-    // Measured in round 3 (OEA_TOPK_SYM_MIN = 8192): on RANDOM unit rows the upper-triangle sweep + list select beat the N x N
-    // strip + three-read row select below 32,768 rows too (15,000 rows, k = 1,499: 1.10 vs 1.39 ms; 30,000 rows, k = 600: 2.29 vs
-    // 3.39 ms, gpurun_out r03p) -- but on TRAINED tables, which is what a refresh sees, the neighbours crowd into few candidate
-    // ranges, list segments overflow and the failed rows are redone through the strip: 1.74 vs 1.41 ms at 15,000 rows in the
-    // bench line (gpurun_out r03r).  The limit stays at 32,768.
-    static const int64_t min_n = [] { const char *e = getenv("OEA_TOPK_SYM_MIN"); return e ? (int64_t)atoll(e) : (int64_t)32768; }();
-    if (n < min_n) return p;
-    const double e = (double)k * kSample / (double)n;
-    p.r = threshold_rank(e);
-    const double frac = (double)p.r / kSample;                  // expected survivor fraction of a row
-    const double m_total = frac * (double)n;
-    if (p.r >= kSample / 2 || m_total * 1.4 > kPerThread * SEL_THREADS || n > (int64_t)kBitWords * 32) return p;
-    p.T = (int)oea::ceil_div(n, 128);
-    p.groups = 16;                                              // work items per (full) query tile row: L tiles each
-    p.L = std::max(8, (int)oea::ceil_div(p.T, p.groups));
-    p.groups = (int)oea::ceil_div(p.T, p.L);
-    p.nseg = 4 * p.groups;
-    if (p.nseg > kMaxSeg || p.nseg + 2 * p.T + 1 >= kMaxSegAll) return p;
-    const double m = frac * p.L * 128.0 / 4.0;                  // per query-side segment (2 wave rows x 2 half-waves share an item)
-    p.cap = ((int)(m * (1.0 + 4.0 / std::sqrt((double)p.r)) + 8.0 * std::sqrt(m) + 32.0) + 7) / 8 * 8;
-    const double mc = frac * 64.0;                              // per candidate-side segment (the 64 queries of one wave column)
-    p.ccap = ((int)(mc * (1.0 + 4.0 / std::sqrt((double)p.r)) + 6.0 * std::sqrt(mc) + 4.0) + 3) / 4 * 4;
-    static const int env_ccap = [] { const char *e = getenv("OEA_TOPK_CCAP"); return e ? atoi(e) : 0; }();       // experiments
-    if (env_ccap >= 4) p.ccap = env_ccap;
-    if (p.ccap > 248 || (size_t)128 * p.nseg * p.cap * 4 >= ((size_t)1 << 31)) return p;
-    int64_t items = 0;
-    for (int c = 0; c < p.groups; ++c) items += std::min(p.T, (c + 1) * p.L);
-    p.n_items = (int)items;
-    p.stride = n / kSample;
-    p.ld = (n + 31) / 32 * 32;
-    auto a256 = [](size_t x) { return (x + 255) / 256 * 256; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += a256(bytes); return o; };
-    p.off_thr = take(sizeof(float) * (size_t)n);
-    p.off_counts = take(sizeof(int32_t) * (size_t)n * p.nseg);
-    p.off_ccounts = take((size_t)n * p.T * 2);
-    p.off_fail = take(sizeof(int32_t) * (size_t)n);
-    p.off_nfail = take(256);
-    p.off_items = take(sizeof(int32_t) * 4 * (size_t)p.n_items);
-    p.off_spcnt = take(sizeof(int32_t) * (size_t)n);
-    p.off_spill = take(8 * (size_t)n * kSpillCap);
-    p.off_vals = take(sizeof(float) * (size_t)n * p.nseg * p.cap);
-    p.off_cols = take(sizeof(int32_t) * (size_t)n * p.nseg * p.cap);
-    p.off_clists = take(8 * (size_t)n * p.T * 2 * p.ccap);
-    p.off_strip = take(sizeof(float) * (size_t)n * kSample);
-    p.total = off;
-    p.ok = off <= ws_bytes;
-    return p;
-}
-
 struct StreamPlan {
     bool ok = false;
     int r = 0, T = 0, L = 0, groups = 0, n_items = 0, rcap = 0, ccap = 0, row_cap = 0, ovf_chunks = 0;
@@ -1283,15 +1215,13 @@ struct StreamPlan {
     int redo_cap = 0;
 };
 
-// the stream form of the symmetric search (bf16 sweep only): same thresholds and work items as plan_sym
+// the stream form of the symmetric search (bf16 sweep only): thresholds as in plan_lists, work items of sym_items_kernel
 static StreamPlan plan_stream(int64_t n, int k, size_t ws_bytes) {
     StreamPlan p;
-    static const bool on = [] {
-        const char *e = getenv("OEA_TOPK_STREAM"), *b = getenv("OEA_TOPK_BF16");      // the streams hold the bf16 sweep's records
-        return !(e && e[0] == '0') && !(b && b[0] == '0');
-    }();
+    // the streams hold the bf16 sweep's records
+    static const bool on = [] { const char *b = getenv("OEA_TOPK_BF16"); return !(b && b[0] == '0'); }();
     // from 12,288 rows on (the 15K datasets: 15,000 rows, k = 1,499: 0.95 ms on random rows / 1.26 ms on the trained table against
-    // 1.21 / 1.31 ms of the N x N strip path; with one bucketing workgroup per tile it lost there)
+    // 1.21 / 1.31 ms of the N x N strip path; with one bucketing workgroup per tile it lost there).  OEA_TOPK_SYM_MIN overrides.
     static const int64_t min_n = [] { const char *e = getenv("OEA_TOPK_SYM_MIN"); return e ? (int64_t)atoll(e) : (int64_t)12288; }();
     if (!on || n < min_n) return p;
     const double e = (double)k * kSample / (double)n;
@@ -1335,10 +1265,10 @@ static StreamPlan plan_stream(int64_t n, int k, size_t ws_bytes) {
     p.off_cstream = take(p.stream_bytes);
     p.off_lists = take(8 * (size_t)p.T * 128 * (size_t)p.row_cap);
     // overflow pool: 40 % of the expected records (both sides) + a chunk per wave
-    p.ovf_chunks = (int)std::min<double>(0.4 * 2.0 * ew * 4.0 * (double)items / kOvfChunkRecs + 4.0 * (double)items, 4.0e6);
-    if (getenv("OEA_TOPK_STREAM_CAP")) p.ovf_chunks = (int)std::min<double>(2.0 * 2.0 * ew * 4.0 * (double)items / kOvfChunkRecs + 8.0 * (double)items, 4.0e6);
+    p.ovf_chunks = (int)std::min<double>(0.4 * 2.0 * ew * 4.0 * (double)items / kOvfChunk + 4.0 * (double)items, 4.0e6);
+    if (getenv("OEA_TOPK_STREAM_CAP")) p.ovf_chunks = (int)std::min<double>(2.0 * 2.0 * ew * 4.0 * (double)items / kOvfChunk + 8.0 * (double)items, 4.0e6);
     if (const char *eo = getenv("OEA_TOPK_OVF_CHUNKS")) p.ovf_chunks = std::max(1, atoi(eo));
-    p.off_ovf = take(16 * (size_t)kOvfChunkRecs * (size_t)p.ovf_chunks);
+    p.off_ovf = take(16 * (size_t)kOvfChunk * (size_t)p.ovf_chunks);
     p.off_ovflen = take(sizeof(int32_t) * (size_t)p.ovf_chunks);
     p.redo_cap = (int)std::min<int64_t>(items * 4 * p.L, 1 << 22);     // (work item, tile, wave) triples: all of them, up to 4 M
     p.off_redo = take(32 * (size_t)p.redo_cap);
@@ -1551,9 +1481,9 @@ __global__ __launch_bounds__(256) void topk_overflow_kernel(const uint4 *__restr
     const int n_chunks = min(*alloc, cap_chunks);
     const int lane = threadIdx.x & 63;
     for (int ch = blockIdx.x * 4 + (threadIdx.x >> 6); ch < n_chunks; ch += gridDim.x * 4) {
-        const int l = min(len[ch], kOvfChunkRecs);
+        const int l = min(len[ch], kOvfChunk);
         for (int i = lane; i < l; i += 64) {
-            const uint4 rec = pool[(size_t)ch * kOvfChunkRecs + i];
+            const uint4 rec = pool[(size_t)ch * kOvfChunk + i];
             const int slot = atomicAdd(counts + rec.y, 1);
             if (slot < row_cap) lists[(size_t)rec.y * row_cap + slot] = make_uint2(rec.x, rec.z);
             else row_fail[rec.y] = 1;
@@ -1710,9 +1640,7 @@ size_t oea_topk_workspace_bytes(int64_t nq, int64_t nc) {
 
 size_t oea_topk_sym_workspace_bytes(int64_t n, int32_t k) {
     const StreamPlan q = plan_stream(n, k, ~(size_t)0);         // the form oea_topk_inner takes when it is covered
-    if (q.ok) return q.total;
-    const SymPlan p = plan_sym(n, k, ~(size_t)0);
-    return p.ok ? p.total : 0;
+    return q.ok ? q.total : 0;
 }
 
 int oea_row_rank_select_f32(const float *vals, int64_t n_rows, int32_t nc, int64_t ld, int32_t k, int32_t largest, const int32_t *ids,
@@ -1759,10 +1687,9 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         if (rc != OEA_OK) return rc;
     }
     static const bool lists_on = [] { const char *e = getenv("OEA_TOPK_LISTS"); return !(e && e[0] == '0'); }();
-    static const bool sym_on = [] { const char *e = getenv("OEA_TOPK_SYM"); return !(e && e[0] == '0'); }();
     const bool same = q == c && nq == nc && ldq == ldc;
     static const bool bf16_sweep = [] { const char *e = getenv("OEA_TOPK_BF16"); return !(e && e[0] == '0'); }();
-    const StreamPlan sp = (same && lists_on && sym_on && bf16_sweep && dim <= 2048) ? plan_stream(nc, k, ws_bytes) : StreamPlan();
+    const StreamPlan sp = (same && lists_on && bf16_sweep && dim <= 2048) ? plan_stream(nc, k, ws_bytes) : StreamPlan();
     if (sp.ok) {                                    // stream form: wave-private record streams -> per-tile bucketing -> compact lists
         char *w = static_cast<char *>(workspace);
         float *thr = reinterpret_cast<float *>(w + sp.off_thr);
@@ -1826,63 +1753,9 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
             fprintf(stderr, "[oea_topk_inner] overflow chunks: %d of %d, redone wave tiles: %d of %d\n", na, sp.ovf_chunks, nr, sp.redo_cap);
         }
         list_select_kernel<<<(unsigned)nq, SEL_THREADS, select_lds_bytes(nc), st>>>(
-            nullptr, nullptr, nullptr, thr, 0, 0, nc, k, id_map, out_idx, fail_rows, n_fail, nullptr, nullptr, 0, 0, nullptr, nullptr,
+            nullptr, nullptr, nullptr, thr, 0, 0, nc, k, id_map, out_idx, fail_rows, n_fail, nullptr, nullptr,
             select_stop(), c, ldc, dim, tol_dev, lists, list_cnt, sp.row_cap, row_fail);
         rc = redo_failed_rows(qp, kp, cp, nc, dim, k, id_map, out_idx, fail_rows, n_fail, w + sp.off_rstream, 2 * sp.stream_bytes, sp.ld, st);
-        if (rc != OEA_OK) return rc;
-        rc = oea::release_packed_rows(st);
-        if (rc != OEA_OK) return rc;
-        OEA_CHECK_HIP(hipGetLastError());
-        return OEA_OK;
-    }
-    const SymPlan sy = (same && lists_on && sym_on && dim <= 2048) ? plan_sym(nc, k, ws_bytes) : SymPlan();
-    if (sy.ok) {                                    // queries == candidates: the upper triangle's tiles feed rows and columns
-        char *w = static_cast<char *>(workspace);
-        float *thr = reinterpret_cast<float *>(w + sy.off_thr);
-        int32_t *counts = reinterpret_cast<int32_t *>(w + sy.off_counts);
-        uint8_t *ccounts = reinterpret_cast<uint8_t *>(w + sy.off_ccounts);
-        int32_t *fail_rows = reinterpret_cast<int32_t *>(w + sy.off_fail);
-        int32_t *n_fail = reinterpret_cast<int32_t *>(w + sy.off_nfail);
-        int32_t *items_dev = reinterpret_cast<int32_t *>(w + sy.off_items);
-        float *list_vals = reinterpret_cast<float *>(w + sy.off_vals);
-        int32_t *list_cols = reinterpret_cast<int32_t *>(w + sy.off_cols);
-        void *clists = w + sy.off_clists;
-        int32_t *spill_cnt = reinterpret_cast<int32_t *>(w + sy.off_spcnt);
-        void *spill = w + sy.off_spill;
-        float *sstrip = reinterpret_cast<float *>(w + sy.off_strip);
-        OEA_REQUIRE(kp <= 4096, "dim <= 4096 on the list path");
-        // work items, chunk-major: (query tile, first candidate tile, one past the last, segment group)
-        sym_items_kernel<<<(unsigned)oea::ceil_div((int64_t)sy.groups * sy.T, 256), 256, 0, st>>>(sy.T, sy.L, sy.groups,
-                                                                                              reinterpret_cast<int4 *>(items_dev));
-        float *sp = nullptr;
-        int kps = 0;
-        int rc = oea::pack_rows(2, c, kSample, ldc * (int)sy.stride, dim, st, &sp, &kps);
-        if (rc != OEA_OK) return rc;
-        oea::sim_inner_store_packed(qp, nq, sp, kSample, kp, dim, sstrip, kSample, st);
-        kth_value_kernel<kSample / 64><<<(unsigned)oea::ceil_div(nq, 4), 256, 0, st>>>(sstrip, nq, kSample, sy.r, thr);
-        OEA_CHECK_HIP(hipMemsetAsync(n_fail, 0, sizeof(int32_t), st));
-        // segments no work item writes (the lower triangle's) must read as empty
-        OEA_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)nq * sy.nseg, st));
-        OEA_CHECK_HIP(hipMemsetAsync(ccounts, 0, (size_t)nq * sy.T * 2, st));
-        OEA_CHECK_HIP(hipMemsetAsync(spill_cnt, 0, sizeof(int32_t) * (size_t)nq, st));
-        // the sweep on the bf16 hi / lo split of the rows (3/16 of the fp32 matrix time; OEA_TOPK_BF16=0: the exact fp32 sweep):
-        // approximate list values, the select decides the neighbourhood of the k-th value with exact chains -- same result
-        static const bool bf16_on = [] { const char *e = getenv("OEA_TOPK_BF16"); return !(e && e[0] == '0'); }();
-        float *tol_dev = reinterpret_cast<float *>(w + sy.off_nfail + 64);
-        if (bf16_on) {
-            rc = oea::topk_append_sym_bf16(c, nc, ldc, dim, thr, items_dev, sy.n_items, sy.nseg, sy.cap, list_vals, list_cols, counts, sy.T,
-                                           sy.ccap, clists, ccounts, spill_cnt, spill, kSpillCap, tol_dev, st);
-            if (rc != OEA_OK) return rc;
-        } else {
-            oea::topk_append_sym_packed(qp, nq, kp, dim, thr, items_dev, sy.n_items, sy.nseg, sy.cap, list_vals, list_cols, counts, sy.T,
-                                        sy.ccap, clists, ccounts, spill_cnt, spill, kSpillCap, st);
-        }
-        list_select_kernel<<<(unsigned)nq, SEL_THREADS, select_lds_bytes(nc), st>>>(
-            list_vals, list_cols, counts, thr, sy.nseg, sy.cap, nc, k, id_map, out_idx, fail_rows, n_fail,
-            static_cast<const uint2 *>(clists), ccounts, 2 * sy.T, sy.ccap, spill_cnt, static_cast<const uint2 *>(spill), select_stop(),
-            c, ldc, dim, bf16_on ? tol_dev : nullptr, nullptr, nullptr, 0, nullptr);
-        rc = redo_failed_rows(qp, kp, cp, nc, dim, k, id_map, out_idx, fail_rows, n_fail, clists,
-                              8 * (size_t)nq * sy.T * 2 * sy.ccap, sy.ld, st);
         if (rc != OEA_OK) return rc;
         rc = oea::release_packed_rows(st);
         if (rc != OEA_OK) return rc;
@@ -1934,11 +1807,9 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
                 oea::topk_append_packed(qp + r0 * kp, rows, cp, nc, kp, dim, thr, lp.cap, lp.chunks, list_vals, list_cols, counts, spill_cnt,
                                         spill, kSpillCap, st);
             list_select_kernel<<<(unsigned)rows, SEL_THREADS, select_lds_bytes(nc), st>>>(
-                list_vals, list_cols, counts, thr, lp.nseg, lp.cap, nc,
-                                                                      k, id_map, out_idx + r0 * (int64_t)k, fail_rows, n_fail, nullptr, nullptr, 0, 0,
-                                                                      spill_cnt, static_cast<const uint2 *>(spill), select_stop(),
-                                                                      bf16_sweep ? c : nullptr, ldc, dim, bf16_sweep ? tol_dev : nullptr,
-                                                                      nullptr, nullptr, 0, nullptr, bf16_sweep ? q + r0 * (int64_t)ldq : nullptr, ldq);
+                list_vals, list_cols, counts, thr, lp.nseg, lp.cap, nc, k, id_map, out_idx + r0 * (int64_t)k, fail_rows, n_fail,
+                spill_cnt, static_cast<const uint2 *>(spill), select_stop(), bf16_sweep ? c : nullptr, ldc, dim,
+                bf16_sweep ? tol_dev : nullptr, nullptr, nullptr, 0, nullptr, bf16_sweep ? q + r0 * (int64_t)ldq : nullptr, ldq);
             // rows the select gave up on: through the strip path, in batches, inside the (now dead) list storage
             rc = redo_failed_rows(qp + r0 * kp, kp, cp, nc, dim, k, id_map, out_idx + r0 * (int64_t)k, fail_rows, n_fail, list_vals,
                                   2 * lp.cols_off, lp.ld, st);

@@ -311,7 +311,7 @@ def test_graph_operators_100k_shape(ops):
 
 def test_symmetric_neighbour_search_equals_general_path(ops):
     """queries == candidates (q is c): only the tiles on and above the diagonal are computed and feed rows and columns
-    (topk_append_sym_kernel); the result equals the general list path's (a copy of the table as candidates) bit for bit,
+    (the stream form: topk_stream_sym_kernel); the result equals the general list path's (a copy of the table as candidates) bit for bit,
     at a size with several work items per query tile and a ragged last tile, and equals the oracle on sampled rows."""
     from oracle import cport
     rng = np.random.RandomState(7)
@@ -326,6 +326,22 @@ def test_symmetric_neighbour_search_equals_general_path(ops):
     assert np.array_equal(sym, gen)
     rows = np.concatenate([[0, 4, 5, n - 1], rng.choice(n, 12, replace=False)])
     assert np.array_equal(sym[rows], cport.topk_inner(emb[rows], emb, k))
+
+
+def test_symmetric_neighbour_search_just_above_the_stream_form(ops):
+    """131,200 rows = 1,025 tiles, one more than the stream form takes: whichever path serves a table against itself there,
+    every row is ascending and unique, holds the row itself, and equals the oracle on sampled rows."""
+    from oracle import cport
+    rng = np.random.RandomState(17)
+    n, d, k = 131200, 32, 1300
+    emb = _unit_rows(rng, n, d)
+    t = ops.to_table(emb)
+    out = ops.topk_inner(t, t, d, k)
+    assert out.shape == (n, k)
+    assert bool((out[:, 1:] > out[:, :-1]).all())                    # ascending, unique per row
+    assert bool((out == torch.arange(n, dtype=torch.int32, device=out.device)[:, None]).any(1).all())
+    rows = np.concatenate([[0, 127, 128, n - 1], rng.choice(n, 12, replace=False)])
+    assert np.array_equal(out[torch.as_tensor(rows, device=out.device)].cpu().numpy(), cport.topk_inner(emb[rows], emb, k))
 
 
 @pytest.mark.parametrize("case", ["tiny streams", "tiny streams, dry pool"])

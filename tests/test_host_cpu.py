@@ -41,13 +41,16 @@ def test_host_side_planners_of_the_library():
     """pure host entry points (no device): workspace planners answer without a GPU and follow their documented domains."""
     from openea_amd import _lib
     lib = _lib.load(require_device=False)
-    # symmetric neighbour search: the stream form from 12,288 rows (round 4), the segment lists from 32,768, up to the select's
-    # segment table (~140,000 rows)
+    # symmetric neighbour search: the stream form from 12,288 rows up to 1,024 tiles of 128 rows (131,072 rows); past either
+    # end the answer is 0 and oea_topk_inner takes the general list path or the strips
     assert lib.oea_topk_sym_workspace_bytes(10000, 200) == 0
     assert 0 < lib.oea_topk_sym_workspace_bytes(15000, 1499) < 2 << 30
     assert 0 < lib.oea_topk_sym_workspace_bytes(20000, 400) < 2 << 30
     need = lib.oea_topk_sym_workspace_bytes(100000, 2000)
-    assert 5 << 30 < need < 12 << 30                # ~8 GB: record streams + compact lists + overflow pool (segment lists: ~30 GB)
+    assert 5 << 30 < need < 12 << 30                # ~8 GB: record streams + compact lists + overflow pool
+    assert lib.oea_topk_sym_workspace_bytes(131072, 2621) > 0
+    assert lib.oea_topk_sym_workspace_bytes(131073, 2621) == 0
+    assert lib.oea_topk_sym_workspace_bytes(135000, 2700) == 0
     assert lib.oea_topk_sym_workspace_bytes(400000, 8000) == 0
     assert lib.oea_topk_workspace_bytes(1000, 100000) == 1000 * 100000 * 4
     # one-sweep CSLS means: from 4,096 x 4,096 on, k <= 32

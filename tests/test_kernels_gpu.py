@@ -1164,7 +1164,8 @@ def test_dense_sgd_any_shape(ops):
 
 @pytest.mark.parametrize("case", ["random", "clusters", "ties"])
 def test_topk_strip_free_path_bit_exact(ops, case, monkeypatch):
-    """nc >= 32,768 and nq >= 4,096 take the threshold-append sweep + list select (no similarity strip in HBM); rows whose
+    """one table against itself at 33,000 rows: no similarity strip in HBM -- the stream form of the symmetric search
+    (upper-triangle sweep, record streams, bucketing, list select); rows whose
     survivor lists overflow / fall short / are tie-heavy are redone by the fallback kernel.  All of it must equal the
     oracle's (value desc, column asc) selection bit for bit -- and the strip path (OEA_TOPK_LISTS=0 is read once per
     process, so the comparison with it is through the oracle)."""
@@ -1185,6 +1186,28 @@ def test_topk_strip_free_path_bit_exact(ops, case, monkeypatch):
     rows = np.concatenate([rng.choice(n, 40, replace=False), np.array([5000, 5001, 7999, 8000, 0, n - 1])])
     ref = cport.topk_inner(x[rows], x, k)
     assert np.array_equal(out[rows], ref * 3 + 1)
+
+
+@pytest.mark.parametrize("d", [40, 75, 100])
+def test_topk_stream_form_every_sweep_instance_equals_strip_path(ops, d):
+    """the stream form's three sweep instances: d = 40 / 75 / 100 pack to Kp = 64 / 96 / 128, i.e. both operands through LDS, and
+    the query operand in registers as 3 and 4 chunks.  12,400 rows is the form's smallest size band with a ragged last tile (112
+    rows); duplicated rows tie inside one tile and across the first and the last.  A copy of the table as candidates takes
+    the N x N strips (nc < 32,768): both must give the same sets on every row, and the oracle's on sampled rows."""
+    from oracle import cport
+    rng = np.random.RandomState(d)
+    n, k = 12400, 250
+    assert ops.lib().oea_topk_sym_workspace_bytes(n, k) > 0
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    x[5] = x[4]
+    x[n - 1] = x[0]
+    t = ops.to_table(x)
+    sym = ops.topk_inner(t, t, d, k).cpu().numpy()
+    strip = ops.topk_inner(t, t.clone(), d, k).cpu().numpy()
+    assert np.array_equal(sym, strip)
+    rows = np.concatenate([[0, 127, 128, 12287, 12288, n - 1], rng.choice(n, 12, replace=False)])
+    assert np.array_equal(sym[rows], cport.topk_inner(x[rows], x, k))
 
 
 @pytest.mark.parametrize("case", ["random", "clusters", "ties", "unnormalised", "d300_k10", "row_block"])

@@ -1,5 +1,5 @@
 """neighbour refresh at the 100K shape on TRAINED tables (clustered embeddings): time per refresh and the rows the list
-paths send to their fallback (OEA_TOPK_DEBUG=1), for the symmetric / general / strip paths (OEA_TOPK_SYM, OEA_TOPK_LISTS)."""
+paths send to their fallback (OEA_TOPK_DEBUG=1), for the stream / general / strip paths (OEA_TOPK_BF16, OEA_TOPK_LISTS)."""
 import os
 import sys
 import time
@@ -21,5 +21,5 @@ for rep in range(3):
     t0 = time.perf_counter()
     refresh_neighbours(wl.ent, wl.kgs.kg1.entities_list, wl.k1)
     torch.cuda.synchronize()
-    print("refresh after %d steps: %.2f ms (SYM=%s LISTS=%s)" % (steps, (time.perf_counter() - t0) * 1e3, os.environ.get("OEA_TOPK_SYM", "1"),
+    print("refresh after %d steps: %.2f ms (BF16=%s LISTS=%s)" % (steps, (time.perf_counter() - t0) * 1e3, os.environ.get("OEA_TOPK_BF16", "1"),
                                                                os.environ.get("OEA_TOPK_LISTS", "1")), flush=True)
