@@ -488,7 +488,8 @@ int oea_sample_negatives_epoch(const int32_t *pos_all, int64_t n_rows, const int
 /* A whole epoch of BasicModel.launch_triple_training_1epo (basic_model.py:222-232) enqueued by
  * ONE call: for step in [0, steps): sample the negatives of batch `step`
  * (oea_sample_negatives_pair with Philox step = step_base + step) and run the fused optimiser
- * step.  pos_all holds the epoch's positive batches back to back; batch `step` is rows
+ * step.  oea_epoch describes the epoch -- what the plain, the partitioned and the boundary-row form of the call share.
+ * pos_all holds the epoch's positive batches back to back; batch `step` is rows
  * [offsets_host[step], offsets_host[step+1]) of it and its first splits_host[step] rows belong
  * to KG1.  k == 0: positive-only losses (MTransE), no sampling.  When offsets_dev / splits_dev (device
  * copies of the two host arrays) are given, neg_buf must hold (total rows)*k triples and the whole
@@ -497,24 +498,38 @@ int oea_sample_negatives_epoch(const int32_t *pos_all, int64_t n_rows, const int
  * layout: neg_buf ALREADY holds the epoch's negatives (drawn by the caller with oea_sample_negatives_epoch, typically
  * on a second stream while the previous epoch was still running).  Nothing is synchronised: the host returns after enqueueing ~3 kernels
  * per step, which removes the per-step host round trip of the reference's feed_dict loop. */
-int oea_triple_epoch(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                     int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                     const int64_t *splits_host, int32_t steps, int32_t k, const oea_sampler_side *side0,
-                     const oea_sampler_side *side1, uint64_t seed, uint32_t step_base, int32_t *neg_buf,
-                     int32_t *err_flag, const oea_step_cfg *cfg, void *workspace, double *loss_accum,
-                     const int64_t *offsets_dev, const int64_t *splits_dev, void *stream);
-/* The same for steps [step_begin, step_end) of the epoch only (a caller that stops or resumes inside an epoch -- e.g.
- * a benchmark timing K steps -- still enqueues them with one call).  step_base is the Philox step of the epoch's
- * step 0.  A range with step_begin == 0 draws the whole epoch's negatives into neg_buf in one launch when the device
- * layout is given; a later range of the same epoch either passes side0 == side1 == NULL (neg_buf still holds them) or
- * both sides (its steps are then drawn again batch by batch -- identical draws). */
-int oea_triple_epoch_range(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                           int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                           const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                           const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                           uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                           void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                           void *stream);
+typedef struct oea_epoch {
+    float *ent, *ent_acc;                /* entity table [n_ent, ld] and its optimiser state; under the entity-id partition */
+    int64_t n_ent;                       /* (_comm / _halo) ent_acc is the state of the OWNED rows only: acc_own [rpr, ld] */
+    float *rel, *rel_acc;
+    int64_t n_rel;
+    int32_t dim, ld;
+    const int32_t *pos_all;              /* the batches */
+    const int64_t *offsets_host, *splits_host;
+    int32_t steps;
+    const int64_t *offsets_dev, *splits_dev;
+    int32_t k;                           /* sampling */
+    const oea_sampler_side *side0, *side1;
+    uint64_t seed;
+    uint32_t step_base;                  /* Philox step of the epoch's step 0 */
+    int32_t *neg_buf, *err_flag;
+    const oea_step_cfg *cfg;
+    void *workspace;
+    double *loss_accum;
+} oea_epoch;
+/* Steps [step_begin, step_end) of the epoch (the whole epoch: 0, steps; a caller that stops or resumes inside an epoch -- e.g.
+ * a benchmark timing K steps -- still enqueues them with one call).  A range with step_begin == 0 draws the whole epoch's
+ * negatives into neg_buf in one launch when the device layout is given; a later range of the same epoch either passes
+ * side0 == side1 == NULL (neg_buf still holds them) or both sides (its steps are then drawn again batch by batch -- identical
+ * draws).
+ *   rank, world  (0, 1: the whole batches)  ONE RANK of a job whose ranks take contiguous shares of every batch (rows
+ *                [n rank / world, n (rank + 1) / world) of the batch's n rows, as models/dist.py:shard_batch) and train on LOCAL
+ *                copies of the tables between two exchanges (`dp_exchange = 'epoch'`: no collective inside the epoch; the caller
+ *                reconciles the copies at the epoch's end).  The negatives keep the single-process Philox streams (position inside
+ *                the batch), so the union of the ranks' draws is the single-process draw.
+ *   plan         (NULL: none; world == 1 only) the workspace of the epoch's gathered-sum plan, see below */
+int oea_triple_epoch_range(const oea_epoch *e, int32_t step_begin, int32_t step_end, int32_t rank, int32_t world, void *plan,
+                           size_t plan_bytes, int32_t plan_built, void *stream);
 
 /* An epoch's shuffle and batch layout in one call (basic_model.py:234-235: random.shuffle of both KGs' relation-triple lists;
  * modules/train/batch.py:17-22: batch s = KG1's slice s then KG2's slice s): triples int32 [n1 + n2, 3] = list 1 then list 2 (never
@@ -549,9 +564,9 @@ int oea_epoch_layout(const int32_t *triples, int64_t n1, int64_t n2, const int64
  *                            scoring kernel takes its positives in that order, so that a workgroup's 8 waves nearly always
  *                            share one relation and sum their relation rows on chip before ONE row of atomics
  *                            (OEA_STEP_REL_ORDER=0: batch order, one row of atomics per positive)
- *   oea_triple_epoch_range_plan  = oea_triple_epoch_range with the plan workspace; plan_built = 0: the call builds the plan itself
- *                            (on `stream`, after drawing the negatives when it draws them); plan == NULL or an unsupported
- *                            configuration: exactly oea_triple_epoch_range. */
+ *   oea_triple_epoch_range   takes the plan workspace as `plan`; plan_built = 0: the call builds the plan itself (on `stream`,
+ *                            after drawing the negatives when it draws them); plan == NULL, world > 1 or an unsupported
+ *                            configuration: the epoch without a plan. */
 int32_t oea_step_plan_supported(const oea_step_cfg *cfg, int64_t n_ent, int64_t n_rel, int32_t ld, int32_t k);
 size_t oea_step_plan_bytes(int64_t n_total, int32_t steps, int64_t max_batch, int64_t n_ent, int32_t ld);
 int oea_step_plan_build(const int32_t *pos_all, const int32_t *neg_all, int32_t k, const int64_t *offsets_dev, int64_t n_total,
@@ -565,41 +580,16 @@ int oea_step_plan_offsets(int64_t n_total, int32_t steps, int64_t max_batch, int
 /* *out = byte offset of rel_order (uint32 [n_total]; for step s, rel_order[offsets[s] + i] = index inside the batch of the step's
  * i-th positive in stable ascending order of relation id = numpy.argsort(relations of the batch, kind="stable")) */
 int oea_step_plan_rel_order_offset(int64_t n_total, int32_t steps, int64_t max_batch, int64_t n_ent, int32_t ld, int64_t *out);
-int oea_triple_epoch_range_plan(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                                int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                                uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                                void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                                void *plan, size_t plan_bytes, int32_t plan_built, void *stream);
-
-/* The same for ONE RANK of a job whose ranks take contiguous shares of every batch (rows [n rank / world, n (rank + 1) / world)
- * of the batch's n rows, as models/dist.py:shard_batch) and train on LOCAL copies of the tables between two exchanges
- * (`dp_exchange = 'epoch'`: no collective inside the epoch; the caller reconciles the copies at the epoch's end).  The
- * negatives keep the single-process Philox streams (position inside the batch), so the union of the ranks' draws is the
- * single-process draw.  rank = 0, world = 1: oea_triple_epoch_range. */
-int oea_triple_epoch_range_shard(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                                 int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                 const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                 const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                                 uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                                 void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                                 int32_t rank, int32_t world, void *stream);
 
 /* The steps [step_begin, step_end) of a data-parallel epoch under the partition from ONE call, over the C ABI's own
  * communicator (oea_comm_*, declared below): per step GRAD on this rank's share of the batch (rows nb*rank/world ..
- * nb*(rank+1)/world of batch s, as oea_triple_epoch_range_shard) -> oea_part_pack -> reduce-scatter + relation all-reduce ->
+ * nb*(rank+1)/world of batch s, as oea_triple_epoch_range's rank / world) -> oea_part_pack -> reduce-scatter + relation all-reduce ->
  * oea_part_apply (+ oea_step_apply_normals for TransH) -> all-gather -> oea_part_unpack, all enqueued on `stream` with no host
  * work in between.  Buffers as above: send [world * rpr * (ld + 1)], own [rpr * (ld + 1)], rel_x [n_rel * (ld + 1)], upd
- * [rpr, ld], all [world, rpr, ld]; acc_own [rpr, ld] (Adagrad).  The other arguments as oea_triple_epoch_range. */
+ * [rpr, ld], all [world, rpr, ld]; e->ent_acc = acc_own [rpr, ld] (Adagrad). */
 struct oea_comm;
-int oea_triple_epoch_range_comm(struct oea_comm *comm, float *ent, float *acc_own, int64_t n_ent, float *rel, float *rel_acc,
-                                int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed, uint32_t step_base,
-                                int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg, void *workspace, double *loss_accum,
-                                const int64_t *offsets_dev, const int64_t *splits_dev, void *send, void *own, void *rel_x,
-                                float *upd, float *all, void *stream);
+int oea_triple_epoch_range_comm(struct oea_comm *comm, const oea_epoch *e, int32_t step_begin, int32_t step_end, void *send, void *own,
+                                void *rel_x, float *upd, float *all, void *stream);
 
 
 /* Negative LINKS of AliNet.generate_input_batch (approaches/alinet.py:988-1006), drawn on the device.
@@ -1116,13 +1106,8 @@ int oea_halo_plan(const int32_t *pos_all, const int32_t *neg_all, int32_t k, con
                   int32_t steps, int32_t step_begin, int32_t step_end, int64_t n_ent, int32_t world, void *halo_ws, size_t halo_ws_bytes,
                   int32_t *counts_host, int32_t *lists_host, int64_t *cap_out, void *stream);
 size_t oea_halo_buffer_bytes(int64_t n_ent, int32_t world, int64_t max_batch, int32_t k, int32_t ld);
-int oea_triple_epoch_range_halo(oea_comm_t comm, float *ent, float *acc_own, int64_t n_ent, float *rel, float *rel_acc,
-                                int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed, uint32_t step_base,
-                                int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg, void *workspace, double *loss_accum,
-                                const int64_t *offsets_dev, const int64_t *splits_dev, void *halo_ws, size_t halo_ws_bytes,
-                                void *buf_a, void *buf_b, size_t buf_bytes, void *rel_x, float *upd, float *all,
+int oea_triple_epoch_range_halo(oea_comm_t comm, const oea_epoch *e, int32_t step_begin, int32_t step_end, void *halo_ws,
+                                size_t halo_ws_bytes, void *buf_a, void *buf_b, size_t buf_bytes, void *rel_x, float *upd, float *all,
                                 int64_t *stats_host, void *stream);
 
 /* Phase times of oea_triple_epoch_range_comm: between _begin and _end every step records HIP events at its phase boundaries

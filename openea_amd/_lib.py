@@ -37,6 +37,17 @@ class SamplerSide(C.Structure):
                 ("filter", C.c_void_p), ("filter_bits", C.c_uint64)]
 
 
+class Epoch(C.Structure):
+    """mirror of `oea_epoch` (include/openea_hip.h): what the three epoch entry points share."""
+    _fields_ = [("ent", C.c_void_p), ("ent_acc", C.c_void_p), ("n_ent", C.c_int64), ("rel", C.c_void_p), ("rel_acc", C.c_void_p),
+                ("n_rel", C.c_int64), ("dim", C.c_int32), ("ld", C.c_int32),
+                ("pos_all", C.c_void_p), ("offsets_host", C.c_void_p), ("splits_host", C.c_void_p), ("steps", C.c_int32),
+                ("offsets_dev", C.c_void_p), ("splits_dev", C.c_void_p),
+                ("k", C.c_int32), ("side0", C.POINTER(SamplerSide)), ("side1", C.POINTER(SamplerSide)), ("seed", C.c_uint64),
+                ("step_base", C.c_uint32), ("neg_buf", C.c_void_p), ("err_flag", C.c_void_p),
+                ("cfg", C.POINTER(StepCfg)), ("workspace", C.c_void_p), ("loss_accum", C.c_void_p)]
+
+
 class CsrSplit(C.Structure):
     """mirror of `oea_csr_split` (include/openea_hip.h)."""
     _fields_ = [("chunk_row", C.c_void_p), ("chunk_e0", C.c_void_p), ("chunk_e1", C.c_void_p), ("rows", C.c_void_p),
@@ -138,15 +149,7 @@ PROTOTYPES = {
                                             _u64, _u32, _u32, _i32, _vp, _vp, _vp]),
     "oea_sample_negatives_epoch": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, C.POINTER(SamplerSide),
                                              C.POINTER(SamplerSide), _u64, _u32, _i32, _vp, _vp, _vp]),
-    "oea_triple_epoch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32,
-                                   C.POINTER(SamplerSide), C.POINTER(SamplerSide), _u64, _u32, _vp, _vp,
-                                   C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp]),
-    "oea_triple_epoch_range": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
-                                         C.POINTER(SamplerSide), C.POINTER(SamplerSide), _u64, _u32, _vp, _vp,
-                                         C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp]),
-    "oea_triple_epoch_range_shard": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
-                                         C.POINTER(SamplerSide), C.POINTER(SamplerSide), _u64, _u32, _vp, _vp,
-                                         C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "oea_triple_epoch_range": (C.c_int, [C.POINTER(Epoch), _i32, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "oea_epoch_layout_bytes": (_sz, [_i64]),
     "oea_epoch_layout": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _u64, _u32, _vp, _vp, _sz, _vp]),
     "oea_step_plan_supported": (_i32, [C.POINTER(StepCfg), _i64, _i64, _i32, _i32]),
@@ -154,12 +157,7 @@ PROTOTYPES = {
     "oea_step_plan_offsets": (C.c_int, [_i64, _i32, _i64, _i64, _i32, _vp]),
     "oea_step_plan_rel_order_offset": (C.c_int, [_i64, _i32, _i64, _i64, _i32, _vp]),
     "oea_step_plan_build": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _sz, _vp]),
-    "oea_triple_epoch_range_plan": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
-                                        C.POINTER(SamplerSide), C.POINTER(SamplerSide), _u64, _u32, _vp, _vp,
-                                        C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
-    "oea_triple_epoch_range_comm": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
-                                        C.POINTER(SamplerSide), C.POINTER(SamplerSide), _u64, _u32, _vp, _vp,
-                                        C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "oea_triple_epoch_range_comm": (C.c_int, [_vp, C.POINTER(Epoch), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "oea_rotate_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "oea_rotate_exchange_doubles": (_sz, [_i64, _i64, _i32]),
     "oea_rotate_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _i32,
@@ -287,9 +285,7 @@ PROTOTYPES = {
     "oea_halo_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64, _i32]),
     "oea_halo_buffer_bytes": (_sz, [_i64, _i32, _i64, _i32, _i32]),
     "oea_halo_plan": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _sz, _vp, _vp, C.POINTER(_i64), _vp]),
-    "oea_triple_epoch_range_halo": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
-                                        C.POINTER(SamplerSide), C.POINTER(SamplerSide), _u64, _u32, _vp, _vp,
-                                        C.POINTER(StepCfg), _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "oea_triple_epoch_range_halo": (C.c_int, [_vp, C.POINTER(Epoch), _i32, _i32, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "oea_comm_profile_begin": (C.c_int, [_vp]),
     "oea_comm_profile_end": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(_i32)]),
 }

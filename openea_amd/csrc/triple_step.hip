@@ -2248,6 +2248,46 @@ static int64_t step_items(const oea_step_cfg &cfg, int64_t n_pos, int64_t n_neg)
     return (grouped || cfg.loss_kind == OEA_LOSS_MARGIN) ? n_pos : n_pos + n_neg;
 }
 
+// how many loss partials the GRAD kernel of a step leaves: one per workgroup of 256 / G groups, G = 32 up to ld 128 and 64 beyond
+// (for_row_width below), none when it scored nothing.  ONE count for launch_step's grid and for everything that adds the partials up
+static int loss_partials(int32_t ld, int64_t n_items) {
+    const int gpb = 256 / (ld <= 128 ? 32 : 64);
+    return n_items > 0 ? (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_items, gpb), 1), kMaxBlocks) : 0;
+}
+
+// The two width ladders.  Each lists its rungs ONCE and hands them to f as std::integral_constant.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// f(G, IT): G-lane groups with IT fragments per lane, by the row length.  ld > 1280: OEA_EUNSUPPORTED, nothing called.
+// Measured and dropped (round 4, run r04f): 64-lane groups for 64 < ld <= 128 (one positive per wave, two fragments
+// per lane): scoring kernel 17.8 -> 20.0 us at the 15K shape, 64.2 -> 60.4 us at the 100K shape, where the 64-lane optimiser
+// kernel loses 18 us against the 16-lane one -- 3 % at best for a second instantiation of every kernel.
+template <class F>
+static int for_row_width(int32_t ld, F &&f) {
+    if (ld <= 32) f(int_c<32>{}, int_c<1>{});
+    else if (ld <= 64) f(int_c<32>{}, int_c<2>{});
+    else if (ld <= 96) f(int_c<32>{}, int_c<3>{});
+    else if (ld <= 128) f(int_c<32>{}, int_c<4>{});
+    else if (ld <= 256) f(int_c<64>{}, int_c<4>{});
+    else if (ld <= 512) f(int_c<64>{}, int_c<8>{});
+    else if (ld <= 1280) f(int_c<64>{}, int_c<20>{});
+    else { oea::set_error("ld %d > 1280 unsupported", ld); return OEA_EUNSUPPORTED; }
+    return OEA_OK;
+}
+
+// f(IT): 16-lane groups (the optimiser kernels where apply_g16 says so, ld <= 128) with IT = ceil(ld / 16) fragments per lane
+template <class F>
+static void for_width16(int32_t ld, F &&f) {
+    const int it16 = (ld + 15) / 16;
+    if (it16 <= 2) f(int_c<2>{});
+    else if (it16 <= 4) f(int_c<4>{});
+    else if (it16 == 5) f(int_c<5>{});
+    else if (it16 == 6) f(int_c<6>{});
+    else if (it16 == 7) f(int_c<7>{});
+    else f(int_c<8>{});
+}
+
 template <int G, int IT>
 int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
                 int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg,
@@ -2262,7 +2302,8 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
     const bool projected = transd || (transh && !transh_grouped);
     const bool grouped = transh_grouped || (!projected && cfg.neg_group_k > 0 && cfg.loss_kind != OEA_LOSS_MARGIN);
     const int64_t items = step_items(cfg, n_pos, n_neg);
-    const int nb1 = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(items, gpb), 1), kMaxBlocks);
+    const int n_part = loss_partials(ld, items);     // (G is for_row_width's: 32 up to ld 128, 64 beyond)
+    const int nb1 = std::max(n_part, 1);
     // profiling events, 4 per STEP: [m0 fwd_bwd m1] ... [m2 apply m3], each pair attached to its kernel's dispatch
     // (oea::launch_timed); a GRAD call takes the first pair and decides whether the step is sampled, the APPLY call
     // that follows takes the second pair
@@ -2300,14 +2341,13 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
                                    ? (float)((double)cfg.lr * std::sqrt(1.0 - std::pow((double)cfg.beta2, t)) / (1.0 - std::pow((double)cfg.beta1, t)))
                                    : cfg.lr;
             oea::launch_events(apply_rows_dense<G, IT>, nb2, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg, ws,
-                              items > 0 ? nb1 : 0, loss_accum, lr_t);
+                              n_part, loss_accum, lr_t);
         } else {
             // rows per lane group: 1.  Measured at the 15K shape (gpurun_out r02a, in-epoch HIP events): R = 1 17.4 us,
             // R = 2 20.1, R = 4 20.4 -- more (shorter) waves hide the row latency better than more loads per wave.
             // OEA_APPLY_ROWS overrides (1 / 2 / 4) for experiments.
             static const int env_r = [] { const char *e = getenv("OEA_APPLY_ROWS"); return e ? atoi(e) : 0; }();
             const int R = env_r ? env_r : 1;
-            const int n_part = items > 0 ? nb1 : 0;   /* no triples scored: no loss partials to add */
             const int folded = phase == OEA_PHASE_APPLY;
             // OEA_APPLY_FLAG_FIRST=1: look at the touched flag before fetching the three rows.  Measured (gpurun_out r02d):
             // 15K shape 11.1 -> 12.8 us, 100K shape 64.0 -> 72.5 us -- a batch touches most of the table at both shapes
@@ -2324,46 +2364,34 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
                 // ONE launch: relation rows | the plan's rows (gathered sums) | flagged rows the plan does not list | loss partials
                 static_assert(kMaxBlocks <= 16 * 256, "the partials block reads 16 per lane");
                 const int64_t bound = 2 * n_pos;                       // at most two distinct rows per positive
-                if (g16 && G == 32) {
-                    const int it16 = (ld + 15) / 16;
-                    const int relb = (int)std::max<int64_t>(oea::ceil_div(n_rel, 16), 1);
-                    const int planb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(bound, 16), 1), 8192);
-                    const int scanb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_ent, 256), 1), 4096);
+                const int pgpb = g16 && G == 32 ? 16 : gpb;
+                const int relb = (int)std::max<int64_t>(oea::ceil_div(n_rel, pgpb), 1);
+                const int planb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(bound, pgpb), 1), 8192);
+                const int scanb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_ent, 256), 1), 4096);
+                auto launch = [&](auto kernel) {
+                    oea::launch_events(kernel, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg,
+                                       ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b, plan->step_first, plan_step,
+                                       plan->inplan, plan->contrib);
+                };
+                if (g16 && G == 32)
+                    for_width16(ld, [&](auto it) {
+                        constexpr int IT16 = decltype(it)::value;
 #ifndef OEA_DET_SCRATCH
-                    // rows as float4 (apply_step_plan_v4); OEA_APPLY_V4=0: dword fragments
-                    static const bool v4 = [] { const char *e = getenv("OEA_APPLY_V4"); return !(e && e[0] == '0'); }();
-#define OEA_APPLYP16(ITX) do { if (v4) oea::launch_events(apply_step_plan_v4<16, ITX>, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg, ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b, plan->step_first, plan_step, plan->inplan, plan->contrib); \
-    else oea::launch_events(apply_step_plan<16, ITX>, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg, ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b, plan->step_first, plan_step, plan->inplan, plan->contrib); } while (0)
-#else
-#define OEA_APPLYP16(ITX) oea::launch_events(apply_step_plan<16, ITX>, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg, ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b, plan->step_first, plan_step, plan->inplan, plan->contrib)
+                        // rows as float4 (apply_step_plan_v4); OEA_APPLY_V4=0: dword fragments
+                        static const bool v4 = [] { const char *e = getenv("OEA_APPLY_V4"); return !(e && e[0] == '0'); }();
+                        if (v4) return launch(apply_step_plan_v4<16, IT16>);
 #endif
-                    if (it16 <= 2) OEA_APPLYP16(2);
-                    else if (it16 <= 4) OEA_APPLYP16(4);
-                    else if (it16 == 5) OEA_APPLYP16(5);
-                    else if (it16 == 6) OEA_APPLYP16(6);
-                    else if (it16 == 7) OEA_APPLYP16(7);
-                    else OEA_APPLYP16(8);
-#undef OEA_APPLYP16
-                } else {
-                    const int relb = (int)std::max<int64_t>(oea::ceil_div(n_rel, gpb), 1);
-                    const int planb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(bound, gpb), 1), 8192);
-                    const int scanb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_ent, 256), 1), 4096);
-                    oea::launch_events(apply_step_plan<G, IT>, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc,
-                                       n_rel, ld, cfg, ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b,
-                                       plan->step_first, plan_step, plan->inplan, plan->contrib);
-                }
+                        launch(apply_step_plan<16, IT16>);
+                    });
+                else
+                    launch(apply_step_plan<G, IT>);
             } else
             if (g16 && G == 32 && R == 1) {
-                const int it16 = (ld + 15) / 16;
                 const int nbg = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_rel + n_ent, 16), 1), 16384);
-#define OEA_APPLY16(ITX) oea::launch_events(apply_rows<16, ITX, 1>, nbg, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg, ws, n_part, loss_accum, folded, flag_first)
-                if (it16 <= 2) OEA_APPLY16(2);
-                else if (it16 <= 4) OEA_APPLY16(4);
-                else if (it16 == 5) OEA_APPLY16(5);
-                else if (it16 == 6) OEA_APPLY16(6);
-                else if (it16 == 7) OEA_APPLY16(7);
-                else OEA_APPLY16(8);
-#undef OEA_APPLY16
+                for_width16(ld, [&](auto it) {
+                    oea::launch_events(apply_rows<16, decltype(it)::value, 1>, nbg, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel,
+                                       ld, cfg, ws, n_part, loss_accum, folded, flag_first);
+                });
             } else
             if (R >= 4 && IT <= 4)
                 oea::launch_events(apply_rows<G, IT, 4>, nb(4), block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg, ws, n_part, loss_accum, folded, flag_first);
@@ -2379,7 +2407,18 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
     return 0;
 }
 
+// 16-lane groups where apply_g16 says so, for_row_width's otherwise: the width of the optimiser kernels of the OWNED rows
+// (part_apply_kernel, halo_apply_kernel) -- the single-GPU job's at this table size (launch_step: G == 32 is ld <= 128)
+template <class F>
+static int for_apply_width(int64_t n_ent, int64_t n_rel, int32_t ld, F &&f) {
+    if (ld > 128 || !apply_g16(n_ent, n_rel, ld)) return for_row_width(ld, f);
+    for_width16(ld, [&](auto it) { f(int_c<16>{}, it); });
+    return OEA_OK;
+}
+
 }  // namespace
+
+#define OEA_TRY_RC(...) do { const int _rc = (__VA_ARGS__); if (_rc != OEA_OK) return _rc; } while (0)
 
 extern "C" {
 
@@ -2394,28 +2433,6 @@ size_t oea_step_exchange_floats(int64_t n_ent, int64_t n_rel, int32_t ld) {
 }
 
 int32_t oea_step_scratch_elem_bytes(void) { return (int32_t)sizeof(grad_t); }
-
-int oea_triple_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc,
-                    int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
-                    const int32_t *neg, int64_t n_neg, const oea_step_cfg *cfg, void *workspace,
-                    double *loss_accum, void *stream) {
-    return oea_triple_step_phase(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n_pos, neg, n_neg, cfg,
-                                 workspace, loss_accum, OEA_PHASE_BOTH, stream);
-}
-
-static int step_phase_impl(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc,
-                           int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
-                           const int32_t *neg, int64_t n_neg, const oea_step_cfg *cfg, void *workspace,
-                           double *loss_accum, int32_t phase, void *stream, const oea::StepPlanView *plan, int plan_step,
-                           int64_t plan_first_pos);
-
-int oea_triple_step_phase(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc,
-                          int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
-                          const int32_t *neg, int64_t n_neg, const oea_step_cfg *cfg, void *workspace,
-                          double *loss_accum, int32_t phase, void *stream) {
-    return step_phase_impl(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n_pos, neg, n_neg, cfg, workspace, loss_accum, phase,
-                           stream, nullptr, 0, 0);
-}
 
 static int step_phase_impl(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc,
                            int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
@@ -2451,21 +2468,29 @@ static int step_phase_impl(float *ent, float *ent_acc, int64_t n_ent, float *rel
     StepWs ws;
     ws_layout(n_ent, n_rel, ld, workspace, &ws);
     hipStream_t st = oea::as_stream(stream);
-#define OEA_STEP(G, IT) launch_step<G, IT>(ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, pos, n_pos, neg, n_neg, *cfg, ws, loss_accum, phase, st, plan, plan_step, plan_first_pos)
-    // Measured and dropped (round 4, gpurun_out r04f): 64-lane groups for 64 < ld <= 128 (one positive per wave, two fragments
-    // per lane): scoring kernel 17.8 -> 20.0 us at the 15K shape, 64.2 -> 60.4 us at the 100K shape, where the 64-lane optimiser
-    // kernel loses 18 us against the 16-lane one -- 3 % at best for a second instantiation of every kernel.
-    if (ld <= 32) OEA_STEP(32, 1);
-    else if (ld <= 64) OEA_STEP(32, 2);
-    else if (ld <= 96) OEA_STEP(32, 3);
-    else if (ld <= 128) OEA_STEP(32, 4);
-    else if (ld <= 256) OEA_STEP(64, 4);
-    else if (ld <= 512) OEA_STEP(64, 8);
-    else if (ld <= 1280) OEA_STEP(64, 20);
-    else { oea::set_error("dim %d > 1280 unsupported", dim); return OEA_EUNSUPPORTED; }
-#undef OEA_STEP
+    const int rc = for_row_width(ld, [&](auto g, auto it) {
+        launch_step<decltype(g)::value, decltype(it)::value>(ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, pos, n_pos, neg, n_neg, *cfg, ws,
+                                                             loss_accum, phase, st, plan, plan_step, plan_first_pos);
+    });
+    if (rc != OEA_OK) { oea::set_error("dim %d > 1280 unsupported", dim); return rc; }
     OEA_CHECK_HIP(hipGetLastError());
     return OEA_OK;
+}
+
+int oea_triple_step_phase(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc,
+                          int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
+                          const int32_t *neg, int64_t n_neg, const oea_step_cfg *cfg, void *workspace,
+                          double *loss_accum, int32_t phase, void *stream) {
+    return step_phase_impl(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n_pos, neg, n_neg, cfg, workspace, loss_accum, phase,
+                           stream, nullptr, 0, 0);
+}
+
+int oea_triple_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc,
+                    int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos,
+                    const int32_t *neg, int64_t n_neg, const oea_step_cfg *cfg, void *workspace,
+                    double *loss_accum, void *stream) {
+    return oea_triple_step_phase(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n_pos, neg, n_neg, cfg,
+                                 workspace, loss_accum, OEA_PHASE_BOTH, stream);
 }
 
 int oea_step_entity_scratch(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, void **ent_grad, void **ent_touched) {
@@ -2495,16 +2520,6 @@ size_t oea_part_send_floats(int64_t n_ent, int32_t ld, int32_t world) {
     return (size_t)world * (size_t)oea_part_rows_per_rank(n_ent, world) * (size_t)(ld + 1);
 }
 
-#define OEA_PART_DISPATCH(CALL)                                         \
-    if (ld <= 32) { CALL(32, 1); }                                      \
-    else if (ld <= 64) { CALL(32, 2); }                                 \
-    else if (ld <= 96) { CALL(32, 3); }                                 \
-    else if (ld <= 128) { CALL(32, 4); }                                \
-    else if (ld <= 256) { CALL(64, 4); }                                \
-    else if (ld <= 512) { CALL(64, 8); }                                \
-    else if (ld <= 1280) { CALL(64, 20); }                              \
-    else { oea::set_error("ld %d > 1280 unsupported", ld); return OEA_EUNSUPPORTED; }
-
 /* TransH under the entity-id partition: the normal-vector table is relation-sized and replicated, so its gradient scratch
  * (copy 0 after the GRAD phase folded the copies) and touched flags are summed over the ranks with two small all-reduces
  * and every rank applies the same update.  oea_step_normal_scratch: where the two regions sit in the workspace (byte
@@ -2526,15 +2541,15 @@ int oea_step_apply_normals(int64_t n_ent, int64_t n_rel, int32_t ld, const oea_s
     StepWs ws;
     ws_layout(n_ent, n_rel, ld, workspace, &ws);
     hipStream_t st = oea::as_stream(stream);
-#define OEA_CALL(G, IT) apply_normal_rows<G, IT><<<(unsigned)std::max<int64_t>(oea::ceil_div(n_rel, 256 / G), 1), 256, 0, st>>>(n_rel, ld, *cfg, ws, 1);
-    OEA_PART_DISPATCH(OEA_CALL)
-#undef OEA_CALL
+    OEA_TRY_RC(for_row_width(ld, [&](auto g, auto it) {
+        constexpr int G = decltype(g)::value;
+        apply_normal_rows<G, decltype(it)::value><<<(unsigned)std::max<int64_t>(oea::ceil_div(n_rel, 256 / G), 1), 256, 0, st>>>(n_rel, ld, *cfg, ws, 1);
+    }));
     OEA_CHECK_HIP(hipGetLastError());
     return OEA_OK;
 }
 
 int64_t oea_step_items(const oea_step_cfg *cfg, int64_t n_pos, int64_t n_neg) { return cfg ? step_items(*cfg, n_pos, n_neg) : -1; }
-
 
 int oea_part_pack(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, int32_t world, void *send_, void *rel_x_,
                   void *stream) {
@@ -2544,11 +2559,11 @@ int oea_part_pack(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, int
     ws_layout(n_ent, n_rel, ld, workspace, &ws);
     const int64_t rpr = oea_part_rows_per_rank(n_ent, world);
     hipStream_t st = oea::as_stream(stream);
-#define OEA_CALL(G, IT)                                                                                                   \
-    part_pack_kernel<G, IT><<<(unsigned)std::min<int64_t>(oea::ceil_div(world * rpr + n_rel, 256 / G), 16384), 256, 0, st>>>( \
-        ws, n_ent, n_rel, ld, world, rpr, send, rel_x)
-    OEA_PART_DISPATCH(OEA_CALL)
-#undef OEA_CALL
+    OEA_TRY_RC(for_row_width(ld, [&](auto g, auto it) {
+        constexpr int G = decltype(g)::value;
+        part_pack_kernel<G, decltype(it)::value><<<(unsigned)std::min<int64_t>(oea::ceil_div(world * rpr + n_rel, 256 / G), 16384), 256, 0, st>>>(
+            ws, n_ent, n_rel, ld, world, rpr, send, rel_x);
+    }));
     OEA_CHECK_HIP(hipGetLastError());
     return OEA_OK;
 }
@@ -2566,29 +2581,14 @@ int oea_part_apply(float *ent, float *acc_own, int64_t n_ent, float *rel, float 
     ws_layout(n_ent, n_rel, ld, workspace, &ws);
     const int64_t rpr = oea_part_rows_per_rank(n_ent, world);
     hipStream_t st = oea::as_stream(stream);
-    // loss partials: one per workgroup of the GRAD kernel that just ran on n_items work items (launch_step's nb1)
-#define OEA_CALL(G, IT)                                                                                                       \
-    {                                                                                                                         \
-        const int gpb = 256 / G;                                                                                              \
-        /* one partial per workgroup of the GRAD kernel, whose groups are 32 lanes wide up to ld = 128 and 64 beyond */     \
-        const int grad_gpb = 256 / (ld <= 128 ? 32 : 64);                                                                     \
-        const int n_part = n_items > 0 ? (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_items, grad_gpb), 1), kMaxBlocks) : 0; \
-        /* the second event pair of a sampled step (the GRAD call took the first): bench.py's apply timing under partitioning */ \
-        oea::launch_timed(part_apply_kernel<G, IT>, (unsigned)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(rpr + n_rel, gpb), 1), 16384), 256, st, \
-            ent, acc_own, n_ent, rel, rel_acc, n_rel, ld, world, rank, rpr, own, rel_x, upd, *cfg, ws, n_part, loss_accum);   \
-    }
-    if (ld <= 128 && apply_g16(n_ent, n_rel, ld)) {                 // the single-GPU job's group width at this table size
-        const int it16 = (ld + 15) / 16;
-        if (it16 <= 2) OEA_CALL(16, 2)
-        else if (it16 <= 4) OEA_CALL(16, 4)
-        else if (it16 == 5) OEA_CALL(16, 5)
-        else if (it16 == 6) OEA_CALL(16, 6)
-        else if (it16 == 7) OEA_CALL(16, 7)
-        else OEA_CALL(16, 8)
-    } else {
-        OEA_PART_DISPATCH(OEA_CALL)
-    }
-#undef OEA_CALL
+    const int n_part = loss_partials(ld, n_items);       // of the GRAD kernel that just ran on n_items work items
+    OEA_TRY_RC(for_apply_width(n_ent, n_rel, ld, [&](auto g, auto it) {
+        constexpr int G = decltype(g)::value;
+        // the second event pair of a sampled step (the GRAD call took the first): bench.py's apply timing under partitioning
+        oea::launch_timed(part_apply_kernel<G, decltype(it)::value>,
+                          (unsigned)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(rpr + n_rel, 256 / G), 1), 16384), 256, st, ent, acc_own,
+                          n_ent, rel, rel_acc, n_rel, ld, world, rank, rpr, own, rel_x, upd, *cfg, ws, n_part, loss_accum);
+    }));
     OEA_CHECK_HIP(hipGetLastError());
     return OEA_OK;
 }
@@ -2603,49 +2603,6 @@ int oea_part_unpack(float *ent, int64_t n_ent, int32_t ld, int32_t world, int32_
     return OEA_OK;
 }
 
-int oea_triple_epoch(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                     int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                     const int64_t *splits_host, int32_t steps, int32_t k, const oea_sampler_side *side0,
-                     const oea_sampler_side *side1, uint64_t seed, uint32_t step_base, int32_t *neg_buf,
-                     int32_t *err_flag, const oea_step_cfg *cfg, void *workspace, double *loss_accum,
-                     const int64_t *offsets_dev, const int64_t *splits_dev, void *stream) {
-    return oea_triple_epoch_range(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos_all, offsets_host, splits_host,
-                                  steps, 0, steps, k, side0, side1, seed, step_base, neg_buf, err_flag, cfg, workspace,
-                                  loss_accum, offsets_dev, splits_dev, stream);
-}
-
-int oea_triple_epoch_range(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                           int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                           const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                           const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                           uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                           void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                           void *stream) {
-    return oea_triple_epoch_range_shard(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos_all, offsets_host, splits_host,
-                                        steps, step_begin, step_end, k, side0, side1, seed, step_base, neg_buf, err_flag, cfg,
-                                        workspace, loss_accum, offsets_dev, splits_dev, 0, 1, stream);
-}
-
-static int epoch_range_impl(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                            int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                            const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                            const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                            uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                            void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                            int32_t rank, int32_t world, void *plan, size_t plan_bytes, int32_t plan_built, void *stream);
-
-int oea_triple_epoch_range_shard(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                                 int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                 const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                 const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                                 uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                                 void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                                 int32_t rank, int32_t world, void *stream) {
-    return epoch_range_impl(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos_all, offsets_host, splits_host, steps, step_begin,
-                            step_end, k, side0, side1, seed, step_base, neg_buf, err_flag, cfg, workspace, loss_accum, offsets_dev,
-                            splits_dev, rank, world, nullptr, 0, 0, stream);
-}
-
 // 1 when an epoch of this configuration would run on the gathered-sum plan (step_plan.h): triple_wave's rule, SGD / Adagrad, the
 // fp32 scratch (the fixed-point build keeps ONE summation path for one GPU and for G ranks), OEA_STEP_PLAN != 0
 int32_t oea_step_plan_supported(const oea_step_cfg *cfg, int64_t n_ent, int64_t n_rel, int32_t ld, int32_t k) {
@@ -2657,174 +2614,77 @@ int32_t oea_step_plan_supported(const oea_step_cfg *cfg, int64_t n_ent, int64_t 
     return wave_rule(*cfg, n_ent, n_rel, ld) && cfg->neg_group_k == k && (cfg->opt_kind == OEA_OPT_SGD || cfg->opt_kind == OEA_OPT_ADAGRAD);
 }
 
-int oea_triple_epoch_range_plan(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                                int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                                uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                                void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                                void *plan, size_t plan_bytes, int32_t plan_built, void *stream) {
-    return epoch_range_impl(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos_all, offsets_host, splits_host, steps, step_begin,
-                            step_end, k, side0, side1, seed, step_base, neg_buf, err_flag, cfg, workspace, loss_accum, offsets_dev,
-                            splits_dev, 0, 1, plan, plan_bytes, plan_built, stream);
-}
+}  // extern "C"
 
-static int epoch_range_impl(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
-                            int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                            const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                            const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed,
-                            uint32_t step_base, int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg,
-                            void *workspace, double *loss_accum, const int64_t *offsets_dev, const int64_t *splits_dev,
-                            int32_t rank, int32_t world, void *plan, size_t plan_bytes, int32_t plan_built, void *stream) {
-    OEA_REQUIRE(pos_all && offsets_host && splits_host && cfg, "null pointer");
-    OEA_REQUIRE(steps >= 0 && k >= 0, "steps, k >= 0");
-    OEA_REQUIRE(0 <= step_begin && step_begin <= step_end && step_end <= steps, "0 <= step_begin <= step_end <= steps");
-    OEA_REQUIRE((offsets_dev == nullptr) == (splits_dev == nullptr), "offsets_dev and splits_dev go together");
+// ---- ONE walk over the batches of an epoch's step range: the plain, the partitioned and the boundary-row epoch ---------------------
+static_assert(sizeof(oea_epoch) == 184, "oea_epoch: openea_amd/_lib.py:Epoch and tests/test_host_cpu.py hold the same layout");
+
+struct EpochStep {                    // a non-empty batch of the range, cut to this rank's share (which may be empty: n == 0)
+    int32_t s;                        // its step inside the epoch
+    int64_t lo, n, r_lo, split;       // rows [lo, lo + n) of pos_all = the batch's rows from r_lo on, the first `split` of them from KG1
+    const int32_t *pos;
+    int32_t *negs;                    // the share's n * k negatives (drawn when the step body runs); NULL when k == 0
+};
+
+struct EpochWalk {
+    const oea_epoch *e;
+    int32_t step_begin, step_end, rank, world;
+    bool presampled, ahead, sample_all;
+    int64_t max_batch;                // the epoch's largest batch
+    oea_step_cfg cfg;                 // the running step's: Adam's opt_t counts the steps actually run (e->cfg->opt_t = count of the first)
+    void *stream;
+};
+
+// validates what the three forms share, decides where the negatives come from and draws the whole epoch's when the range starts it
+static int epoch_walk_begin(const oea_epoch *e, int32_t step_begin, int32_t step_end, int32_t rank, int32_t world, void *stream,
+                            EpochWalk *w) {
+    OEA_REQUIRE(e && e->pos_all && e->offsets_host && e->splits_host && e->cfg, "null pointer");
+    OEA_REQUIRE(e->steps >= 0 && e->k >= 0, "steps, k >= 0");
+    OEA_REQUIRE(0 <= step_begin && step_begin <= step_end && step_end <= e->steps, "0 <= step_begin <= step_end <= steps");
+    OEA_REQUIRE((e->offsets_dev == nullptr) == (e->splits_dev == nullptr), "offsets_dev and splits_dev go together");
     OEA_REQUIRE(world >= 1 && rank >= 0 && rank < world, "0 <= rank < world");
+    const int32_t k = e->k, steps = e->steps;
     // side0 == NULL with the device layout given: neg_buf already holds the epoch's negatives (the caller drew them
     // with oea_sample_negatives_epoch, e.g. on another stream while the previous epoch was running)
-    const bool presampled = k > 0 && side0 == nullptr && side1 == nullptr && offsets_dev != nullptr;
-    OEA_REQUIRE(k == 0 || (neg_buf && (presampled || (err_flag && side0 && side1))), "sampling needs neg_buf, err_flag and both sides");
-    const bool ahead = k > 0 && offsets_dev != nullptr && steps > 0;      // neg_buf covers the whole epoch
+    const bool presampled = k > 0 && e->side0 == nullptr && e->side1 == nullptr && e->offsets_dev != nullptr;
+    OEA_REQUIRE(k == 0 || (e->neg_buf && (presampled || (e->err_flag && e->side0 && e->side1))),
+                "sampling needs neg_buf, err_flag and both sides");
+    const bool ahead = k > 0 && e->offsets_dev != nullptr && steps > 0;      // neg_buf covers the whole epoch
     // the sampler does not read the tables: a range that starts the epoch draws ALL its negatives in one launch
     // (later ranges of the same epoch find them in neg_buf: pass side0 = side1 = NULL, or let them be drawn again
     // step by step -- the Philox streams are the same either way).  A rank of a sharded job draws the WHOLE epoch as
     // well (same streams on every rank: the union of the ranks' slices is the single-process draw) and uses its rows.
     const bool sample_all = ahead && !presampled && step_begin == 0;
-    if (sample_all) {
-        const int rc = oea_sample_negatives_epoch(pos_all, offsets_host[steps], offsets_dev, splits_dev, steps, k, side0,
-                                                  side1, seed, step_base, 10, neg_buf, err_flag, stream);
-        if (rc != OEA_OK) return rc;
-    }
-    // the gathered-sum plan (step_plan.h): needs the whole epoch's negatives to exist before its first step
-    oea::StepPlanView pv;
-    const bool use_plan = plan && world == 1 && ahead && (presampled || sample_all) && oea_step_plan_supported(cfg, n_ent, n_rel, ld, k);
-    if (use_plan) {
-        int64_t max_batch = 0;
-        for (int32_t s = 0; s < steps; ++s) max_batch = std::max(max_batch, offsets_host[s + 1] - offsets_host[s]);
-        const size_t need = oea::step_plan_layout(offsets_host[steps], steps, max_batch, n_ent, ld, plan, &pv);
-        OEA_REQUIRE(plan_bytes >= need, "plan workspace smaller than oea_step_plan_bytes");
-        if (!plan_built) {
-            const int rc = oea_step_plan_build(pos_all, neg_buf, k, offsets_dev, offsets_host[steps], steps, max_batch, n_ent, ld, plan,
-                                               plan_bytes, stream);
-            if (rc != OEA_OK) return rc;
-        }
-    }
-    oea_step_cfg step_cfg = *cfg;             // Adam: opt_t counts the steps actually run (cfg->opt_t = count of the first)
-    for (int32_t s = step_begin; s < step_end; ++s) {
-        const int64_t b0 = offsets_host[s], nb = offsets_host[s + 1] - b0;
+    if (sample_all)
+        OEA_TRY_RC(oea_sample_negatives_epoch(e->pos_all, e->offsets_host[steps], e->offsets_dev, e->splits_dev, steps, k, e->side0, e->side1,
+                                              e->seed, e->step_base, 10, e->neg_buf, e->err_flag, stream));
+    int64_t max_batch = 0;
+    for (int32_t s = 0; s < steps; ++s) max_batch = std::max(max_batch, e->offsets_host[s + 1] - e->offsets_host[s]);
+    *w = EpochWalk{e, step_begin, step_end, rank, world, presampled, ahead, sample_all, max_batch, *e->cfg, stream};
+    return OEA_OK;
+}
+
+// step(EpochStep) -> OEA_* for every non-empty batch of the range, with w.cfg the step's configuration
+template <class F>
+static int epoch_walk(EpochWalk &w, F &&step) {
+    const oea_epoch &e = *w.e;
+    for (int32_t s = w.step_begin; s < w.step_end; ++s) {
+        const int64_t b0 = e.offsets_host[s], nb = e.offsets_host[s + 1] - b0;
         if (nb <= 0) continue;
         // this rank's contiguous share of the batch rows (models/dist.py:shard_batch; the whole batch when world == 1)
-        const int64_t r_lo = nb * rank / world, r_hi = nb * (rank + 1) / world;
+        const int64_t r_lo = nb * w.rank / w.world, r_hi = nb * (w.rank + 1) / w.world;
         const int64_t lo = b0 + r_lo, n = r_hi - r_lo;
-        int64_t split = splits_host[s] - r_lo;
-        split = split < 0 ? 0 : (split > n ? n : split);
-        const int32_t *pos = pos_all + 3 * lo;
-        int32_t *negs = ahead ? neg_buf + 3 * lo * (int64_t)k : neg_buf;
-        if (n > 0 && k > 0 && !presampled && !sample_all) {
-            const int rc = oea_sample_negatives_pair(pos, n, split, k, side0, side1, seed, step_base + (uint32_t)s,
-                                                     (uint32_t)r_lo, 10, negs, err_flag, stream);
-            if (rc != OEA_OK) return rc;
-        }
-        if (n > 0) {
-            const int rc = step_phase_impl(ent, ent_acc, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n,
-                                           k > 0 ? negs : nullptr, n * (int64_t)k, &step_cfg, workspace, loss_accum,
-                                           OEA_PHASE_BOTH, stream, use_plan ? &pv : nullptr, s, lo);
-            if (rc != OEA_OK) return rc;
-        }
-        ++step_cfg.opt_t;
+        const int64_t split = std::min(std::max<int64_t>(e.splits_host[s] - r_lo, 0), n);
+        int32_t *negs = e.k == 0 ? nullptr : w.ahead ? e.neg_buf + 3 * lo * (int64_t)e.k : e.neg_buf;
+        const EpochStep t{s, lo, n, r_lo, split, e.pos_all + 3 * lo, negs};
+        if (n > 0 && e.k > 0 && !w.presampled && !w.sample_all)
+            OEA_TRY_RC(oea_sample_negatives_pair(t.pos, n, split, e.k, e.side0, e.side1, e.seed, e.step_base + (uint32_t)s, (uint32_t)r_lo, 10,
+                                                 negs, e.err_flag, w.stream));
+        OEA_TRY_RC(step(t));
+        ++w.cfg.opt_t;
     }
     return OEA_OK;
 }
-
-// The steps [step_begin, step_end) of a data-parallel epoch under the entity-id partition, enqueued by ONE call: per step
-// GRAD on this rank's share of the batch -> pack -> reduce-scatter (RCCL) + all-reduce of the relation rows -> optimiser on
-// the owned rows -> all-gather -> unpack; everything on `stream`, no host work between the steps (driven from Python the
-// exchange costs six library calls and three torch.distributed calls per step).  The communicator is the C ABI's own
-// (oea_comm_*: RCCL through dlopen), so a non-Python host runs the same job.  Buffers as in the step-by-step protocol
-// (include/openea_hip.h): send [world * rpr * (ld + 1)], own [rpr * (ld + 1)], rel_x [n_rel * (ld + 1)], upd [rpr, ld],
-// all [world, rpr, ld]; acc_own = the optimiser state of the owned rows.  TransH: the normal vectors' scratch is all-reduced
-// and applied on every rank.  Same Philox streams as the single-GPU epoch; result = the step-by-step partitioned job.
-int oea_triple_epoch_range_comm(oea_comm_t comm, float *ent, float *acc_own, int64_t n_ent, float *rel, float *rel_acc,
-                                int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed, uint32_t step_base,
-                                int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg, void *workspace, double *loss_accum,
-                                const int64_t *offsets_dev, const int64_t *splits_dev, void *send, void *own, void *rel_x,
-                                float *upd, float *all, void *stream) {
-    OEA_REQUIRE(comm && pos_all && offsets_host && splits_host && cfg && send && own && rel_x && upd && all, "null pointer");
-    OEA_REQUIRE(steps >= 0 && k >= 0 && 0 <= step_begin && step_begin <= step_end && step_end <= steps, "step range");
-    OEA_REQUIRE((offsets_dev == nullptr) == (splits_dev == nullptr), "offsets_dev and splits_dev go together");
-    OEA_REQUIRE(cfg->opt_kind == OEA_OPT_SGD || cfg->opt_kind == OEA_OPT_ADAGRAD, "the partition runs SGD / Adagrad");
-    const int32_t world = oea_comm_size(comm), rank = oea_comm_rank(comm);
-    const bool presampled = k > 0 && side0 == nullptr && side1 == nullptr && offsets_dev != nullptr;
-    OEA_REQUIRE(k == 0 || (neg_buf && (presampled || (err_flag && side0 && side1))), "sampling needs neg_buf, err_flag and both sides");
-    const bool ahead = k > 0 && offsets_dev != nullptr && steps > 0;
-    const bool sample_all = ahead && !presampled && step_begin == 0;
-    if (sample_all) {
-        const int rc = oea_sample_negatives_epoch(pos_all, offsets_host[steps], offsets_dev, splits_dev, steps, k, side0, side1, seed,
-                                                  step_base, 10, neg_buf, err_flag, stream);
-        if (rc != OEA_OK) return rc;
-    }
-    const int64_t rpr = oea_part_rows_per_rank(n_ent, world);
-    const int64_t chunk = rpr * (ld + 1);
-    const bool transh = cfg->score_kind == OEA_SCORE_TRANSH;
-    void *nrm_grad = nullptr, *nrm_touched = nullptr;
-    if (transh) {
-        int64_t g_off = 0, t_off = 0;
-        int rc = oea_step_normal_scratch(n_ent, n_rel, ld, &g_off, &t_off);
-        if (rc != OEA_OK) return rc;
-        nrm_grad = static_cast<char *>(workspace) + g_off;
-        nrm_touched = static_cast<char *>(workspace) + t_off;
-    }
-    // the gradients travel in the scratch's own type: fp32, or int64 fixed point in the deterministic build (exact sums:
-    // the G-rank job then equals the single-GPU job bit for bit)
-    const int32_t gdt = oea::kDetScratch ? OEA_COMM_I64 : OEA_COMM_F32;
-    hipStream_t st = oea::as_stream(stream);
-    oea_step_cfg step_cfg = *cfg;
-#define OEA_TRY_RC(call) do { const int _rc = (call); if (_rc != OEA_OK) return _rc; } while (0)
-    for (int32_t s = step_begin; s < step_end; ++s) {
-        const int64_t b0 = offsets_host[s], nb = offsets_host[s + 1] - b0;
-        if (nb <= 0) continue;
-        const int64_t r_lo = nb * rank / world, r_hi = nb * (rank + 1) / world;
-        const int64_t lo = b0 + r_lo, n = r_hi - r_lo;
-        int64_t split = splits_host[s] - r_lo;
-        split = split < 0 ? 0 : (split > n ? n : split);
-        const int32_t *pos = pos_all + 3 * lo;
-        int32_t *negs = ahead ? neg_buf + 3 * lo * (int64_t)k : neg_buf;
-        if (n > 0 && k > 0 && !presampled && !sample_all)
-            OEA_TRY_RC(oea_sample_negatives_pair(pos, n, split, k, side0, side1, seed, step_base + (uint32_t)s, (uint32_t)r_lo, 10, negs,
-                                                 err_flag, stream));
-        // every rank takes part in every exchange, also with an empty share of the batch (n == 0: nothing scored)
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        OEA_TRY_RC(oea_triple_step_phase(ent, nullptr, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n, k > 0 ? negs : nullptr, n * (int64_t)k,
-                                         &step_cfg, workspace, loss_accum, OEA_PHASE_GRAD, stream));
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        OEA_TRY_RC(oea_part_pack(workspace, n_ent, n_rel, ld, world, send, rel_x, stream));
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        OEA_TRY_RC(oea_comm_reduce_scatter(comm, send, own, chunk, gdt, stream));
-        OEA_TRY_RC(oea_comm_allreduce(comm, rel_x, n_rel * (int64_t)(ld + 1), gdt, stream));
-        if (transh) {
-            OEA_TRY_RC(oea_comm_allreduce(comm, nrm_grad, n_rel * (int64_t)ld, gdt, stream));
-            OEA_TRY_RC(oea_comm_allreduce(comm, nrm_touched, n_rel, gdt, stream));
-        }
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        const int64_t n_items = step_items(step_cfg, n, n * (int64_t)k);
-        OEA_TRY_RC(oea_part_apply(ent, acc_own, n_ent, rel, rel_acc, n_rel, ld, world, rank, own, rel_x, upd, &step_cfg, workspace, n_items,
-                                  loss_accum, stream));
-        if (transh) OEA_TRY_RC(oea_step_apply_normals(n_ent, n_rel, ld, &step_cfg, workspace, stream));
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        OEA_TRY_RC(oea_allgather_rows(comm, upd, all, rpr, ld, stream));
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        OEA_TRY_RC(oea_part_unpack(ent, n_ent, ld, world, rank, all, stream));
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        ++step_cfg.opt_t;
-    }
-#undef OEA_TRY_RC
-    return OEA_OK;
-}
-
-}  // extern "C"
 
 // ---- the halo form of the one-call partitioned epoch ---------------------------------------------------------------------------------
 static HaloGeom halo_geom(int64_t n_ent, int32_t world, int32_t rank, int64_t max_batch, int32_t k) {
@@ -2854,7 +2714,99 @@ static size_t halo_ws_layout(const HaloGeom &g, int32_t steps, void *base, HaloW
     return off;
 }
 
+// the row lists of steps [step_begin, step_end): who refers to which rows in which step -> hw.lists / hw.counts, hw.err = overflow
+static int halo_build_lists(const int32_t *pos_all, const int32_t *neg_all, int32_t k, const int64_t *offsets_host,
+                            const int64_t *offsets_dev, int32_t step_begin, int32_t step_end, const HaloGeom &g, const HaloWs &hw,
+                            hipStream_t st) {
+    const int32_t nS = step_end - step_begin;
+    OEA_CHECK_HIP(hipMemsetAsync(hw.bitmaps, 0, 4 * (size_t)nS * g.world * g.nwords, st));
+    OEA_CHECK_HIP(hipMemsetAsync(hw.err, 0, 4, st));
+    const int64_t rows = offsets_host[step_end] - offsets_host[step_begin];
+    if (rows > 0)
+        halo_mark_kernel<<<(unsigned)std::min<int64_t>(oea::ceil_div(rows * (k + 1), 256), 16384), 256, 0, st>>>(
+            pos_all, neg_all, k, offsets_dev, step_begin, step_end, g, hw.bitmaps);
+    halo_compact_kernel<<<(unsigned)(nS * g.world), 256, 0, st>>>(hw.bitmaps, g, hw.lists, hw.counts, hw.err);
+    return OEA_OK;
+}
+
 extern "C" {
+
+int oea_triple_epoch_range(const oea_epoch *e, int32_t step_begin, int32_t step_end, int32_t rank, int32_t world, void *plan,
+                           size_t plan_bytes, int32_t plan_built, void *stream) {
+    EpochWalk w;
+    OEA_TRY_RC(epoch_walk_begin(e, step_begin, step_end, rank, world, stream, &w));
+    // the gathered-sum plan (step_plan.h): needs the whole epoch's negatives to exist before its first step
+    oea::StepPlanView pv;
+    const bool use_plan = plan && world == 1 && w.ahead && (w.presampled || w.sample_all) &&
+                          oea_step_plan_supported(e->cfg, e->n_ent, e->n_rel, e->ld, e->k);
+    if (use_plan) {
+        const int64_t n_total = e->offsets_host[e->steps];
+        const size_t need = oea::step_plan_layout(n_total, e->steps, w.max_batch, e->n_ent, e->ld, plan, &pv);
+        OEA_REQUIRE(plan_bytes >= need, "plan workspace smaller than oea_step_plan_bytes");
+        if (!plan_built)
+            OEA_TRY_RC(oea_step_plan_build(e->pos_all, e->neg_buf, e->k, e->offsets_dev, n_total, e->steps, w.max_batch, e->n_ent, e->ld, plan,
+                                           plan_bytes, stream));
+    }
+    return epoch_walk(w, [&](const EpochStep &t) -> int {
+        if (t.n == 0) return OEA_OK;
+        return step_phase_impl(e->ent, e->ent_acc, e->n_ent, e->rel, e->rel_acc, e->n_rel, e->dim, e->ld, t.pos, t.n, t.negs,
+                               t.n * (int64_t)e->k, &w.cfg, e->workspace, e->loss_accum, OEA_PHASE_BOTH, stream,
+                               use_plan ? &pv : nullptr, t.s, t.lo);
+    });
+}
+
+// The steps [step_begin, step_end) of a data-parallel epoch under the entity-id partition, enqueued by ONE call: per step
+// GRAD on this rank's share of the batch -> pack -> reduce-scatter (RCCL) + all-reduce of the relation rows -> optimiser on
+// the owned rows -> all-gather -> unpack; everything on `stream`, no host work between the steps (driven from Python the
+// exchange costs six library calls and three torch.distributed calls per step).  The communicator is the C ABI's own
+// (oea_comm_*: RCCL through dlopen), so a non-Python host runs the same job.  Buffers as in the step-by-step protocol
+// (include/openea_hip.h): send [world * rpr * (ld + 1)], own [rpr * (ld + 1)], rel_x [n_rel * (ld + 1)], upd [rpr, ld],
+// all [world, rpr, ld]; e->ent_acc = the optimiser state of the owned rows.  TransH: the normal vectors' scratch is all-reduced
+// and applied on every rank.  Same Philox streams as the single-GPU epoch; result = the step-by-step partitioned job.
+int oea_triple_epoch_range_comm(oea_comm_t comm, const oea_epoch *e, int32_t step_begin, int32_t step_end, void *send, void *own,
+                                void *rel_x, float *upd, float *all, void *stream) {
+    OEA_REQUIRE(comm && e && e->pos_all && e->offsets_host && e->splits_host && e->cfg && send && own && rel_x && upd && all, "null pointer");
+    OEA_REQUIRE(e->steps >= 0 && e->k >= 0 && 0 <= step_begin && step_begin <= step_end && step_end <= e->steps, "step range");
+    OEA_REQUIRE(e->cfg->opt_kind == OEA_OPT_SGD || e->cfg->opt_kind == OEA_OPT_ADAGRAD, "the partition runs SGD / Adagrad");
+    const int32_t world = oea_comm_size(comm), rank = oea_comm_rank(comm);
+    EpochWalk w;
+    OEA_TRY_RC(epoch_walk_begin(e, step_begin, step_end, rank, world, stream, &w));
+    const int64_t n_ent = e->n_ent, n_rel = e->n_rel;
+    const int32_t ld = e->ld, k = e->k;
+    const int64_t rpr = oea_part_rows_per_rank(n_ent, world);
+    const int64_t chunk = rpr * (ld + 1);
+    const bool transh = e->cfg->score_kind == OEA_SCORE_TRANSH;
+    StepWs ws;                                 // (TransH: where the normals' scratch and flags sit)
+    ws_layout(n_ent, n_rel, ld, e->workspace, &ws);
+    // the gradients travel in the scratch's own type: fp32, or int64 fixed point in the deterministic build (exact sums:
+    // the G-rank job then equals the single-GPU job bit for bit)
+    const int32_t gdt = oea::kDetScratch ? OEA_COMM_I64 : OEA_COMM_F32;
+    hipStream_t st = oea::as_stream(stream);
+    return epoch_walk(w, [&](const EpochStep &t) -> int {
+        // every rank takes part in every exchange, also with an empty share of the batch (n == 0: nothing scored)
+        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
+        OEA_TRY_RC(oea_triple_step_phase(e->ent, nullptr, n_ent, e->rel, e->rel_acc, n_rel, e->dim, ld, t.pos, t.n, t.negs, t.n * (int64_t)k,
+                                         &w.cfg, e->workspace, e->loss_accum, OEA_PHASE_GRAD, stream));
+        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
+        OEA_TRY_RC(oea_part_pack(e->workspace, n_ent, n_rel, ld, world, send, rel_x, stream));
+        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
+        OEA_TRY_RC(oea_comm_reduce_scatter(comm, send, own, chunk, gdt, stream));
+        OEA_TRY_RC(oea_comm_allreduce(comm, rel_x, n_rel * (int64_t)(ld + 1), gdt, stream));
+        if (transh) {
+            OEA_TRY_RC(oea_comm_allreduce(comm, ws.nrm_grad, n_rel * (int64_t)ld, gdt, stream));
+            OEA_TRY_RC(oea_comm_allreduce(comm, ws.nrm_touched, n_rel, gdt, stream));
+        }
+        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
+        OEA_TRY_RC(oea_part_apply(e->ent, e->ent_acc, n_ent, e->rel, e->rel_acc, n_rel, ld, world, rank, own, rel_x, upd, &w.cfg, e->workspace,
+                                  step_items(w.cfg, t.n, t.n * (int64_t)k), e->loss_accum, stream));
+        if (transh) OEA_TRY_RC(oea_step_apply_normals(n_ent, n_rel, ld, &w.cfg, e->workspace, stream));
+        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
+        OEA_TRY_RC(oea_allgather_rows(comm, upd, all, rpr, ld, stream));
+        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
+        OEA_TRY_RC(oea_part_unpack(e->ent, n_ent, ld, world, rank, all, stream));
+        return oea::comm_phase_mark(comm, st);
+    });
+}
 
 size_t oea_halo_workspace_bytes(int64_t n_ent, int32_t world, int32_t steps, int64_t max_batch, int32_t k) {
     if (world < 1 || steps < 0) return 0;
@@ -2888,13 +2840,7 @@ int oea_halo_plan(const int32_t *pos_all, const int32_t *neg_all, int32_t k, con
     if (nS == 0) return OEA_OK;
     HaloWs hw;
     OEA_REQUIRE(halo_ws_bytes >= halo_ws_layout(g, nS, halo_ws, &hw), "halo workspace smaller than oea_halo_workspace_bytes");
-    OEA_CHECK_HIP(hipMemsetAsync(hw.bitmaps, 0, 4 * (size_t)nS * world * g.nwords, st));
-    OEA_CHECK_HIP(hipMemsetAsync(hw.err, 0, 4, st));
-    const int64_t rows = offsets_host[step_end] - offsets_host[step_begin];
-    if (rows > 0)
-        halo_mark_kernel<<<(unsigned)std::min<int64_t>(oea::ceil_div(rows * (k + 1), 256), 16384), 256, 0, st>>>(
-            pos_all, neg_all, k, offsets_dev, step_begin, step_end, g, hw.bitmaps);
-    halo_compact_kernel<<<(unsigned)(nS * world), 256, 0, st>>>(hw.bitmaps, g, hw.lists, hw.counts, hw.err);
+    OEA_TRY_RC(halo_build_lists(pos_all, neg_all, k, offsets_host, offsets_dev, step_begin, step_end, g, hw, st));
     int32_t err = 0;
     OEA_CHECK_HIP(hipMemcpyAsync(counts_host, hw.counts, 4 * (size_t)nS * world * world, hipMemcpyDeviceToHost, st));
     if (lists_host) OEA_CHECK_HIP(hipMemcpyAsync(lists_host, hw.lists, 4 * (size_t)nS * world * g.cap, hipMemcpyDeviceToHost, st));
@@ -2904,48 +2850,35 @@ int oea_halo_plan(const int32_t *pos_all, const int32_t *neg_all, int32_t k, con
     return OEA_OK;
 }
 
-int oea_triple_epoch_range_halo(oea_comm_t comm, float *ent, float *acc_own, int64_t n_ent, float *rel, float *rel_acc,
-                                int64_t n_rel, int32_t dim, int32_t ld, const int32_t *pos_all, const int64_t *offsets_host,
-                                const int64_t *splits_host, int32_t steps, int32_t step_begin, int32_t step_end, int32_t k,
-                                const oea_sampler_side *side0, const oea_sampler_side *side1, uint64_t seed, uint32_t step_base,
-                                int32_t *neg_buf, int32_t *err_flag, const oea_step_cfg *cfg, void *workspace, double *loss_accum,
-                                const int64_t *offsets_dev, const int64_t *splits_dev, void *halo_ws, size_t halo_ws_bytes,
-                                void *buf_a, void *buf_b, size_t buf_bytes, void *rel_x, float *upd, float *all,
+int oea_triple_epoch_range_halo(oea_comm_t comm, const oea_epoch *e, int32_t step_begin, int32_t step_end, void *halo_ws,
+                                size_t halo_ws_bytes, void *buf_a, void *buf_b, size_t buf_bytes, void *rel_x, float *upd, float *all,
                                 int64_t *stats_host, void *stream) {
-    OEA_REQUIRE(comm && ent && rel && pos_all && offsets_host && splits_host && cfg && workspace && loss_accum && halo_ws && buf_a && buf_b &&
-                rel_x && upd && all, "null pointer");
-    OEA_REQUIRE(steps >= 0 && k >= 0 && 0 <= step_begin && step_begin <= step_end && step_end <= steps, "step range");
-    OEA_REQUIRE(offsets_dev && splits_dev, "the halo exchange plans from the epoch's batches on the device: offsets_dev / splits_dev");
-    OEA_REQUIRE(cfg->opt_kind == OEA_OPT_SGD || cfg->opt_kind == OEA_OPT_ADAGRAD, "the partition runs SGD / Adagrad");
-    OEA_REQUIRE(cfg->score_kind == OEA_SCORE_TRANSE || cfg->score_kind == OEA_SCORE_TRANSH, "halo exchange: TransE / TransH scores");
-    OEA_REQUIRE(ld % 4 == 0, "ld % 4 == 0");
+    OEA_REQUIRE(comm && e && e->ent && e->rel && e->pos_all && e->offsets_host && e->splits_host && e->cfg && e->workspace && e->loss_accum &&
+                halo_ws && buf_a && buf_b && rel_x && upd && all, "null pointer");
+    OEA_REQUIRE(e->steps >= 0 && e->k >= 0 && 0 <= step_begin && step_begin <= step_end && step_end <= e->steps, "step range");
+    OEA_REQUIRE(e->offsets_dev && e->splits_dev, "the halo exchange plans from the epoch's batches on the device: offsets_dev / splits_dev");
+    OEA_REQUIRE(e->cfg->opt_kind == OEA_OPT_SGD || e->cfg->opt_kind == OEA_OPT_ADAGRAD, "the partition runs SGD / Adagrad");
+    OEA_REQUIRE(e->cfg->score_kind == OEA_SCORE_TRANSE || e->cfg->score_kind == OEA_SCORE_TRANSH, "halo exchange: TransE / TransH scores");
+    OEA_REQUIRE(e->ld % 4 == 0, "ld % 4 == 0");
     const int32_t world = oea_comm_size(comm), rank = oea_comm_rank(comm);
-    const bool presampled = k > 0 && side0 == nullptr && side1 == nullptr;
-    OEA_REQUIRE(k == 0 || (neg_buf && (presampled || (err_flag && side0 && side1))), "sampling needs neg_buf, err_flag and both sides");
-    OEA_REQUIRE(k == 0 || presampled || step_begin == 0, "the whole epoch's negatives are drawn by the range that starts it");
+    EpochWalk w;
+    OEA_TRY_RC(epoch_walk_begin(e, step_begin, step_end, rank, world, stream, &w));
+    // (a range that does not start the epoch drew nothing above: its steps would be sampled one by one, after the lists are built)
+    OEA_REQUIRE(e->k == 0 || w.presampled || step_begin == 0, "the whole epoch's negatives are drawn by the range that starts it");
+    const int64_t n_ent = e->n_ent, n_rel = e->n_rel;
+    const int32_t ld = e->ld, k = e->k;
+    const int64_t *offsets_host = e->offsets_host;
+    float *ent = e->ent;
     hipStream_t st = oea::as_stream(stream);
-    if (k > 0 && !presampled) {
-        const int rc = oea_sample_negatives_epoch(pos_all, offsets_host[steps], offsets_dev, splits_dev, steps, k, side0, side1, seed,
-                                                  step_base, 10, neg_buf, err_flag, stream);
-        if (rc != OEA_OK) return rc;
-    }
     const int32_t nS = step_end - step_begin;
     if (stats_host) { stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0; }
     if (nS == 0) return OEA_OK;
-    int64_t max_batch = 0;
-    for (int32_t s = 0; s < steps; ++s) max_batch = std::max(max_batch, offsets_host[s + 1] - offsets_host[s]);
-    const HaloGeom g = halo_geom(n_ent, world, rank, max_batch, k);
+    const HaloGeom g = halo_geom(n_ent, world, rank, w.max_batch, k);
     HaloWs hw;
     OEA_REQUIRE(halo_ws_bytes >= halo_ws_layout(g, nS, halo_ws, &hw), "halo workspace smaller than oea_halo_workspace_bytes(n_ent, world, steps, max_batch, k)");
-    OEA_REQUIRE(buf_bytes >= oea_halo_buffer_bytes(n_ent, world, max_batch, k, ld), "exchange buffers smaller than oea_halo_buffer_bytes");
+    OEA_REQUIRE(buf_bytes >= oea_halo_buffer_bytes(n_ent, world, w.max_batch, k, ld), "exchange buffers smaller than oea_halo_buffer_bytes");
     // ---- plan: who refers to which rows in which step (every rank computes the same tables) -----------------------------------
-    OEA_CHECK_HIP(hipMemsetAsync(hw.bitmaps, 0, 4 * (size_t)nS * world * g.nwords, st));
-    OEA_CHECK_HIP(hipMemsetAsync(hw.err, 0, 4, st));
-    const int64_t rows = offsets_host[step_end] - offsets_host[step_begin];
-    if (rows > 0)
-        halo_mark_kernel<<<(unsigned)std::min<int64_t>(oea::ceil_div(rows * (k + 1), 256), 16384), 256, 0, st>>>(
-            pos_all, neg_buf, k, offsets_dev, step_begin, step_end, g, hw.bitmaps);
-    halo_compact_kernel<<<(unsigned)(nS * world), 256, 0, st>>>(hw.bitmaps, g, hw.lists, hw.counts, hw.err);
+    OEA_TRY_RC(halo_build_lists(e->pos_all, e->neg_buf, k, offsets_host, e->offsets_dev, step_begin, step_end, g, hw, st));
     std::vector<int32_t> counts((size_t)nS * world * world + 1);
     OEA_CHECK_HIP(hipMemcpyAsync(counts.data(), hw.counts, 4 * (size_t)nS * world * world, hipMemcpyDeviceToHost, st));
     OEA_CHECK_HIP(hipMemcpyAsync(counts.data() + (size_t)nS * world * world, hw.err, 4, hipMemcpyDeviceToHost, st));
@@ -2966,44 +2899,30 @@ int oea_triple_epoch_range_halo(oea_comm_t comm, float *ent, float *acc_own, int
     OEA_CHECK_HIP(hipMemcpyAsync(hw.tables, tables.data(), 4 * tables.size(), hipMemcpyHostToDevice, st));
     OEA_CHECK_HIP(hipStreamSynchronize(st));                          // (tables lives on this stack frame)
     const int64_t rpr = g.rpr;
-    const bool transh = cfg->score_kind == OEA_SCORE_TRANSH;
-    void *nrm_grad = nullptr, *nrm_touched = nullptr;
-    if (transh) {
-        int64_t g_off = 0, t_off = 0;
-        const int rc = oea_step_normal_scratch(n_ent, n_rel, ld, &g_off, &t_off);
-        if (rc != OEA_OK) return rc;
-        nrm_grad = static_cast<char *>(workspace) + g_off;
-        nrm_touched = static_cast<char *>(workspace) + t_off;
-    }
+    const bool transh = e->cfg->score_kind == OEA_SCORE_TRANSH;
     const int32_t gdt = oea::kDetScratch ? OEA_COMM_I64 : OEA_COMM_F32;
     StepWs ws;
-    ws_layout(n_ent, n_rel, ld, workspace, &ws);
+    ws_layout(n_ent, n_rel, ld, e->workspace, &ws);
     grad_t *xa = static_cast<grad_t *>(buf_a), *xb = static_cast<grad_t *>(buf_b), *relx = static_cast<grad_t *>(rel_x);
     std::vector<int64_t> sc(world), sd(world), rc_(world), rd(world);
-    oea_step_cfg step_cfg = *cfg;
-#define OEA_TRY_RC(call) do { const int _rc = (call); if (_rc != OEA_OK) return _rc; } while (0)
-    for (int32_t s = step_begin; s < step_end; ++s) {
+    OEA_TRY_RC(epoch_walk(w, [&](const EpochStep &t) -> int {
+        const int32_t s = t.s;
         const int sl = s - step_begin;
-        const int64_t b0 = offsets_host[s], nb = offsets_host[s + 1] - b0;
-        if (nb <= 0) continue;
-        const int64_t r_lo = nb * rank / world, r_hi = nb * (rank + 1) / world;
-        const int64_t lo = b0 + r_lo, n = r_hi - r_lo;
-        const int32_t *pos = pos_all + 3 * lo;
-        int32_t *negs = k > 0 ? neg_buf + 3 * lo * (int64_t)k : nullptr;
         const int32_t *tab = hw.tables + (size_t)sl * 4 * (world + 1);
         const int32_t *t0h = tables.data() + (size_t)sl * 4 * (world + 1), *t1h = t0h + (world + 1);
         OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        OEA_TRY_RC(oea_triple_step_phase(ent, nullptr, n_ent, rel, rel_acc, n_rel, dim, ld, pos, n, negs, n * (int64_t)k, &step_cfg, workspace,
-                                         loss_accum, OEA_PHASE_GRAD, stream));
+        OEA_TRY_RC(oea_triple_step_phase(ent, nullptr, n_ent, e->rel, e->rel_acc, n_rel, e->dim, ld, t.pos, t.n, t.negs, t.n * (int64_t)k, &w.cfg,
+                                         e->workspace, e->loss_accum, OEA_PHASE_GRAD, stream));
         OEA_TRY_RC(oea::comm_phase_mark(comm, st));
         // ---- PUSH -------------------------------------------------------------------------------------------------------------
         const int64_t n_send = t0h[world], n_recv = t1h[world];
         const int32_t *list_me = hw.lists + ((size_t)sl * world + rank) * g.cap, *lists_s = hw.lists + (size_t)sl * world * g.cap;
-#define OEA_CALL(G, IT)                                                                                                             \
-        if (n_send > 0) halo_push_pack_kernel<G, IT><<<(unsigned)std::min<int64_t>(oea::ceil_div(n_send, 256 / G), 16384), 256, 0, st>>>( \
-            ws, ld, g, list_me, tab, xa);
-        OEA_PART_DISPATCH(OEA_CALL)
-#undef OEA_CALL
+        OEA_TRY_RC(for_row_width(ld, [&](auto gw, auto it) {
+            constexpr int G = decltype(gw)::value;
+            if (n_send > 0)
+                halo_push_pack_kernel<G, decltype(it)::value><<<(unsigned)std::min<int64_t>(oea::ceil_div(n_send, 256 / G), 16384), 256, 0, st>>>(
+                    ws, ld, g, list_me, tab, xa);
+        }));
         halo_rel_pack_kernel<<<(unsigned)std::min<int64_t>(oea::ceil_div(n_rel * (int64_t)ld, 256), 4096), 256, 0, st>>>(ws, n_rel, ld, relx);
         halo_rel_flags_kernel<<<(unsigned)oea::ceil_div(n_rel, 256), 256, 0, st>>>(ws, n_rel, ld, relx);
         OEA_TRY_RC(oea::comm_phase_mark(comm, st));
@@ -3016,8 +2935,8 @@ int oea_triple_epoch_range_halo(oea_comm_t comm, float *ent, float *acc_own, int
         OEA_TRY_RC(oea_comm_alltoallv(comm, xa, sc.data(), sd.data(), xb, rc_.data(), rd.data(), gdt, stream));
         OEA_TRY_RC(oea_comm_allreduce(comm, relx, n_rel * (int64_t)(ld + 1), gdt, stream));
         if (transh) {
-            OEA_TRY_RC(oea_comm_allreduce(comm, nrm_grad, n_rel * (int64_t)ld, gdt, stream));
-            OEA_TRY_RC(oea_comm_allreduce(comm, nrm_touched, n_rel, gdt, stream));
+            OEA_TRY_RC(oea_comm_allreduce(comm, ws.nrm_grad, n_rel * (int64_t)ld, gdt, stream));
+            OEA_TRY_RC(oea_comm_allreduce(comm, ws.nrm_touched, n_rel, gdt, stream));
         }
         if (stats_host) {
             int64_t out_rows = 0;
@@ -3027,33 +2946,21 @@ int oea_triple_epoch_range_halo(oea_comm_t comm, float *ent, float *acc_own, int
             stats_host[3] += 1;
         }
         OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-#define OEA_CALL(G, IT)                                                                                                             \
-        if (n_recv > 0) halo_push_unpack_kernel<G, IT><<<(unsigned)std::min<int64_t>(oea::ceil_div(n_recv, 256 / G), 16384), 256, 0, st>>>( \
-            ws, ld, g, lists_s, tab + 2 * (world + 1), tab + (world + 1), xb);
-        OEA_PART_DISPATCH(OEA_CALL)
-#undef OEA_CALL
+        OEA_TRY_RC(for_row_width(ld, [&](auto gw, auto it) {
+            constexpr int G = decltype(gw)::value;
+            if (n_recv > 0)
+                halo_push_unpack_kernel<G, decltype(it)::value><<<(unsigned)std::min<int64_t>(oea::ceil_div(n_recv, 256 / G), 16384), 256, 0, st>>>(
+                    ws, ld, g, lists_s, tab + 2 * (world + 1), tab + (world + 1), xb);
+        }));
         // ---- optimiser on the owned rows (the single-GPU job's group width at this table size) ---------------------------------
-        const int64_t n_items = step_items(step_cfg, n, n * (int64_t)k);
-        {
-            const int grad_gpb = 256 / (ld <= 128 ? 32 : 64);
-            const int n_part = n_items > 0 ? (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_items, grad_gpb), 1), kMaxBlocks) : 0;
-#define OEA_CALL(G, IT)                                                                                                             \
-            oea::launch_timed(halo_apply_kernel<G, IT>, (unsigned)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(rpr + n_rel, 256 / G), 1), 16384), \
-                              256, st, ent, acc_own, n_ent, rel, rel_acc, n_rel, ld, world, rank, rpr, relx, step_cfg, ws, n_part, loss_accum);
-            if (ld <= 128 && apply_g16(n_ent, n_rel, ld)) {
-                const int it16 = (ld + 15) / 16;
-                if (it16 <= 2) { OEA_CALL(16, 2) }
-                else if (it16 <= 4) { OEA_CALL(16, 4) }
-                else if (it16 == 5) { OEA_CALL(16, 5) }
-                else if (it16 == 6) { OEA_CALL(16, 6) }
-                else if (it16 == 7) { OEA_CALL(16, 7) }
-                else { OEA_CALL(16, 8) }
-            } else {
-                OEA_PART_DISPATCH(OEA_CALL)
-            }
-#undef OEA_CALL
-        }
-        if (transh) OEA_TRY_RC(oea_step_apply_normals(n_ent, n_rel, ld, &step_cfg, workspace, stream));
+        const int n_part = loss_partials(ld, step_items(w.cfg, t.n, t.n * (int64_t)k));
+        OEA_TRY_RC(for_apply_width(n_ent, n_rel, ld, [&](auto gw, auto it) {
+            constexpr int G = decltype(gw)::value;
+            oea::launch_timed(halo_apply_kernel<G, decltype(it)::value>,
+                              (unsigned)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(rpr + n_rel, 256 / G), 1), 16384), 256, st, ent,
+                              e->ent_acc, n_ent, e->rel, e->rel_acc, n_rel, ld, world, rank, rpr, relx, w.cfg, ws, n_part, e->loss_accum);
+        }));
+        if (transh) OEA_TRY_RC(oea_step_apply_normals(n_ent, n_rel, ld, &w.cfg, e->workspace, stream));
         OEA_TRY_RC(oea::comm_phase_mark(comm, st));
         // ---- PULL for the next step of the range: the current values of the rows its readers refer to ---------------------------
         int32_t s2 = s + 1;
@@ -3090,10 +2997,8 @@ int oea_triple_epoch_range_halo(oea_comm_t comm, float *ent, float *acc_own, int
             OEA_TRY_RC(oea::comm_phase_mark(comm, st));
             OEA_TRY_RC(oea_part_unpack(ent, n_ent, ld, world, rank, all, stream));
         }
-        OEA_TRY_RC(oea::comm_phase_mark(comm, st));
-        ++step_cfg.opt_t;
-    }
-#undef OEA_TRY_RC
+        return oea::comm_phase_mark(comm, st);
+    }));
     OEA_CHECK_HIP(hipGetLastError());
     return OEA_OK;
 }

@@ -5,7 +5,7 @@ This is what replaces the reference's producer processes + queue + feed_dict +
 (``BasicModel.launch_triple_training_1epo``, models/basic_model.py:211-236): positives,
 triple membership set, neighbour lists, tables, optimiser state and the loss accumulator all
 live in HBM; an epoch = one sampler launch for all its batches (both KGs, batch.py:36-45) + two kernels per step,
-enqueued by one C call (oea_triple_epoch).
+enqueued by one C call (oea_triple_epoch_range).
 
 Multi-GPU (torch.distributed, backend nccl = RCCL): tables are replicated, each rank scores
 its own slice of every batch, the gradient scratch is summed with ONE all-reduce per step and
@@ -427,7 +427,7 @@ class RelationTripleEpochs:
 
     def run_epoch(self, trainer):
         """All `triple_steps` steps of one epoch.  Single GPU: one C call enqueues the whole epoch
-        (oea_triple_epoch); data parallel (or a trainer without the fused epoch call, fused_epoch = False): per-step loop
+        (oea_triple_epoch_range); data parallel (or a trainer without the fused epoch call, fused_epoch = False): per-step loop
         with the exchange between the phases."""
         assert self.in_epoch == 0, "run_epoch in the middle of an epoch: use run_steps"
         return self.run_steps(trainer, len(self.batches.splits))
@@ -476,40 +476,31 @@ class RelationTripleEpochs:
             # an epoch whose negatives were dropped (set_neighbours between two run_steps calls) takes the dense exchange, which
             # samples step by step
             halo_ok = (not self.k) or have or lo == 0
-            if c_part and getattr(trainer, "exchange", None) == "halo" and halo_ok:
+            use_halo = c_part and getattr(trainer, "exchange", None) == "halo" and halo_ok
+            if use_halo and getattr(self, "_off_dev", None) is None:          # (k = 0: no negatives buffer made them)
+                self._off_dev = torch.from_numpy(b.offsets).to(self.dev)
+                self._spl_dev = torch.from_numpy(b.splits).to(self.dev)
+            sides = (None, None) if (have or not self.k) else self._sides
+            dev_layout = (self._off_dev, self._spl_dev) if (self.k or use_halo) else (None, None)
+            # what the three calls share, behind the entity table and its optimiser state (the whole table's, or the owned rows')
+            shared = (trainer.rel.var, trainer.rel_acc, trainer.ent.dim, b.dall, b.offsets, b.splits, self.k, sides[0], sides[1], self.seed,
+                      self._epoch_base, self._neg_all if self.k else None, self.err if self.k else None, trainer.cfg, trainer.ws,
+                      trainer.loss) + dev_layout
+            if use_halo:
                 halo = trainer.halo_buffers(S, int(np.diff(b.offsets).max()), self.k)
-                if getattr(self, "_off_dev", None) is None:          # (k = 0: no negatives buffer made them)
-                    self._off_dev = torch.from_numpy(b.offsets).to(self.dev)
-                    self._spl_dev = torch.from_numpy(b.splits).to(self.dev)
-                st = ops.triple_epoch_halo(trainer.comm.handle, trainer.ent.var, trainer.part['acc_own'], trainer.rel.var, trainer.rel_acc,
-                                           trainer.ent.dim, b.dall, b.offsets, b.splits, self.k,
-                                           None if (have or not self.k) else self._sides[0],
-                                           None if (have or not self.k) else self._sides[1], self.seed, self._epoch_base,
-                                           self._neg_all if self.k else None, self.err if self.k else None, trainer.cfg,
-                                           trainer.ws, trainer.loss, self._off_dev, self._spl_dev, trainer.part, halo, step_range=(lo, hi))
+                st = ops.triple_epoch_halo(trainer.comm.handle, trainer.ent.var, trainer.part['acc_own'], *shared, trainer.part, halo,
+                                           step_range=(lo, hi))
                 trainer.halo_stats = [trainer.halo_stats[0] + st[0], trainer.halo_stats[1] + st[1], max(trainer.halo_stats[2], st[2]),
                                       trainer.halo_stats[3] + st[3]]
             elif c_part:
-                ops.triple_epoch_comm(trainer.comm.handle, trainer.ent.var, trainer.part['acc_own'], trainer.rel.var, trainer.rel_acc,
-                                      trainer.ent.dim, b.dall, b.offsets, b.splits, self.k,
-                                      None if (have or not self.k) else self._sides[0],
-                                      None if (have or not self.k) else self._sides[1], self.seed, self._epoch_base,
-                                      self._neg_all if self.k else None, self.err if self.k else None, trainer.cfg,
-                                      trainer.ws, trainer.loss, self._off_dev if self.k else None,
-                                      self._spl_dev if self.k else None, trainer.part, step_range=(lo, hi))
+                ops.triple_epoch_comm(trainer.comm.handle, trainer.ent.var, trainer.part['acc_own'], *shared, trainer.part, step_range=(lo, hi))
             else:
                 plan = None
                 if self.world == 1 and not local and self.k and self._plan_wanted(trainer):
                     # the epoch's gathered-sum plan (include/openea_hip.h): sorted on the side stream with the negatives it is
                     # built from (_prefetch_next), or by the call itself when it draws them (first epoch, after a refresh)
                     plan = (self._plan, self._plan_ready and bool(have))
-                ops.triple_epoch(trainer.ent.var, trainer.ent_acc, trainer.rel.var, trainer.rel_acc, trainer.ent.dim,
-                                 b.dall, b.offsets, b.splits, self.k,
-                                 None if (have or not self.k) else self._sides[0],
-                                 None if (have or not self.k) else self._sides[1], self.seed, self._epoch_base,
-                                 self._neg_all if self.k else None, self.err if self.k else None, trainer.cfg,
-                                 trainer.ws, trainer.loss, self._off_dev if self.k else None,
-                                 self._spl_dev if self.k else None, step_range=(lo, hi),
+                ops.triple_epoch(trainer.ent.var, trainer.ent_acc, *shared, step_range=(lo, hi),
                                  shard=(self.rank, self.world) if local else (0, 1), plan=plan)
                 if plan is not None and (have or lo == 0):
                     self._plan_ready = True               # built by the call (or already there) for the rest of this epoch

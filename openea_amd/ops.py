@@ -631,33 +631,33 @@ def sample_negatives_epoch(pos_all, offsets_dev, splits_dev, steps, k, side0, si
     return out
 
 
+def _epoch(ent, ent_acc, rel, rel_acc, dim, pos_all, offsets, splits, k, side0, side1, seed, step_base, neg_buf, err_flag, cfg,
+           workspace, loss_accum, offsets_dev, splits_dev, step_range):
+    """-> (_lib.Epoch, lo, hi): the descriptor the three epoch calls share (oea_epoch) and the step range, default the whole epoch"""
+    offsets, splits = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(splits, np.int64)   # what the C side reads
+    steps = len(splits)
+    e = _lib.Epoch(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim, ent.shape[1],
+                   _p(pos_all), offsets.ctypes.data, splits.ctypes.data, steps, _p(offsets_dev), _p(splits_dev),
+                   int(k), C.pointer(side0) if side0 is not None else None, C.pointer(side1) if side1 is not None else None,
+                   int(seed), int(step_base), _p(neg_buf), _p(err_flag), C.pointer(cfg), _p(workspace), _p(loss_accum))
+    e._keep = (offsets, splits)
+    lo, hi = (0, steps) if step_range is None else step_range
+    return e, int(lo), int(hi)
+
+
 def triple_epoch(ent, ent_acc, rel, rel_acc, dim, pos_all, offsets, splits, k, side0, side1, seed, step_base,
                  neg_buf, err_flag, cfg, workspace, loss_accum, offsets_dev=None, splits_dev=None, step_range=None, shard=(0, 1),
                  plan=None):
     """Enqueue every step of an epoch (or steps [lo, hi) of it: step_range) with one call (offsets / splits: host int64
     numpy arrays; their device copies enable sampling the whole epoch ahead in one launch -- neg_buf then covers the
     epoch).  step_base: Philox step of the epoch's step 0.  shard = (rank, world): this rank's contiguous share of every
-    batch, trained on the local tables (dp_exchange = 'epoch')."""
-    steps = len(splits)
-    lo, hi = (0, steps) if step_range is None else step_range
-    if plan is not None and tuple(shard) == (0, 1):
-        # the gathered-sum plan of the epoch (step_plan_buffer / step_plan_build; include/openea_hip.h): plan = (buffer, built)
-        check(lib().oea_triple_epoch_range_plan(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim,
-                                                ent.shape[1], _p(pos_all), offsets.ctypes.data_as(C.c_void_p),
-                                                splits.ctypes.data_as(C.c_void_p), steps, int(lo), int(hi), int(k),
-                                                C.byref(side0) if side0 is not None else None,
-                                                C.byref(side1) if side1 is not None else None, int(seed), int(step_base),
-                                                _p(neg_buf), _p(err_flag), C.byref(cfg), _p(workspace), _p(loss_accum),
-                                                _p(offsets_dev), _p(splits_dev), _p(plan[0]), plan[0].numel(), int(bool(plan[1])),
-                                                _stream()))
-        return
-    check(lib().oea_triple_epoch_range_shard(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim,
-                                       ent.shape[1], _p(pos_all), offsets.ctypes.data_as(C.c_void_p),
-                                       splits.ctypes.data_as(C.c_void_p), steps, int(lo), int(hi), int(k),
-                                       C.byref(side0) if side0 is not None else None,
-                                       C.byref(side1) if side1 is not None else None, int(seed), int(step_base),
-                                       _p(neg_buf), _p(err_flag), C.byref(cfg), _p(workspace), _p(loss_accum),
-                                       _p(offsets_dev), _p(splits_dev), int(shard[0]), int(shard[1]), _stream()))
+    batch, trained on the local tables (dp_exchange = 'epoch').  plan = (buffer, built): the gathered-sum plan of the epoch
+    (step_plan_buffer / step_plan_build; include/openea_hip.h), for shard (0, 1) only."""
+    e, lo, hi = _epoch(ent, ent_acc, rel, rel_acc, dim, pos_all, offsets, splits, k, side0, side1, seed, step_base, neg_buf, err_flag,
+                       cfg, workspace, loss_accum, offsets_dev, splits_dev, step_range)
+    buf, built = plan if plan is not None else (None, False)
+    check(lib().oea_triple_epoch_range(C.byref(e), lo, hi, int(shard[0]), int(shard[1]), _p(buf), buf.numel() if buf is not None else 0,
+                                       int(bool(built)), _stream()))
 
 
 def epoch_layout(triples, n1, n2, slot, seed, epoch, dall, workspace=None):
@@ -748,16 +748,9 @@ def triple_epoch_comm(comm, ent, acc_own, rel, rel_acc, dim, pos_all, offsets, s
                       err_flag, cfg, workspace, loss_accum, offsets_dev, splits_dev, bufs, step_range=None):
     """steps [lo, hi) of a data-parallel epoch under the entity-id partition from ONE C call over the C ABI's communicator
     (oea_triple_epoch_range_comm); bufs = part_buffers(...)."""
-    offsets, splits = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(splits, np.int64)   # what the C side reads
-    steps = len(splits)
-    lo, hi = (0, steps) if step_range is None else step_range
-    check(lib().oea_triple_epoch_range_comm(comm, _p(ent), _p(acc_own), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim,
-                                            ent.shape[1], _p(pos_all), offsets.ctypes.data_as(C.c_void_p),
-                                            splits.ctypes.data_as(C.c_void_p), steps, int(lo), int(hi), int(k),
-                                            C.byref(side0) if side0 is not None else None,
-                                            C.byref(side1) if side1 is not None else None, int(seed), int(step_base),
-                                            _p(neg_buf), _p(err_flag), C.byref(cfg), _p(workspace), _p(loss_accum),
-                                            _p(offsets_dev), _p(splits_dev), _p(bufs['send']), _p(bufs['own']), _p(bufs['rel_x']),
+    e, lo, hi = _epoch(ent, acc_own, rel, rel_acc, dim, pos_all, offsets, splits, k, side0, side1, seed, step_base, neg_buf, err_flag,
+                       cfg, workspace, loss_accum, offsets_dev, splits_dev, step_range)
+    check(lib().oea_triple_epoch_range_comm(comm, C.byref(e), lo, hi, _p(bufs['send']), _p(bufs['own']), _p(bufs['rel_x']),
                                             _p(bufs['upd']), _p(bufs['all']), _stream()))
 
 
@@ -796,18 +789,11 @@ def triple_epoch_halo(comm, ent, acc_own, rel, rel_acc, dim, pos_all, offsets, s
                       err_flag, cfg, workspace, loss_accum, offsets_dev, splits_dev, bufs, halo, step_range=None):
     """triple_epoch_comm with the boundary-row exchange (oea_triple_epoch_range_halo); bufs = part_buffers(...), halo =
     halo_buffers(...) -> (bytes pushed, bytes pulled, largest rows sent in a step, steps) of this rank"""
-    offsets, splits = np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(splits, np.int64)   # what the C side reads
-    steps = len(splits)
-    lo, hi = (0, steps) if step_range is None else step_range
+    e, lo, hi = _epoch(ent, acc_own, rel, rel_acc, dim, pos_all, offsets, splits, k, side0, side1, seed, step_base, neg_buf, err_flag,
+                       cfg, workspace, loss_accum, offsets_dev, splits_dev, step_range)
     stats = (C.c_int64 * 4)()
-    check(lib().oea_triple_epoch_range_halo(comm, _p(ent), _p(acc_own), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim,
-                                            ent.shape[1], _p(pos_all), offsets.ctypes.data_as(C.c_void_p),
-                                            splits.ctypes.data_as(C.c_void_p), steps, int(lo), int(hi), int(k),
-                                            C.byref(side0) if side0 is not None else None,
-                                            C.byref(side1) if side1 is not None else None, int(seed), int(step_base),
-                                            _p(neg_buf), _p(err_flag), C.byref(cfg), _p(workspace), _p(loss_accum),
-                                            _p(offsets_dev), _p(splits_dev), _p(halo['ws']), halo['ws'].numel(), _p(halo['a']),
-                                            _p(halo['b']), halo['a'].numel(), _p(bufs['rel_x']), _p(bufs['upd']), _p(bufs['all']),
+    check(lib().oea_triple_epoch_range_halo(comm, C.byref(e), lo, hi, _p(halo['ws']), halo['ws'].numel(), _p(halo['a']), _p(halo['b']),
+                                            halo['a'].numel(), _p(bufs['rel_x']), _p(bufs['upd']), _p(bufs['all']),
                                             C.cast(stats, C.c_void_p), _stream()))
     return tuple(int(x) for x in stats)
 

@@ -152,50 +152,51 @@ sys.path.insert(0, os.environ["OEA_ROOT"])
 from openea_amd import ops
 from openea_amd.models.trainer import EmbeddingTable, TripleTrainer
 torch.cuda.set_device(0)
-rng = np.random.RandomState(7)
-n_ent, n_rel, d, B, k, steps = 1003, 19, 40, 900, 3, 5
-ent_h = (rng.standard_normal((n_ent, d)) / np.sqrt(d)).astype(np.float32)
-rel_h = (rng.standard_normal((n_rel, d)) / np.sqrt(d)).astype(np.float32)
-pos = np.stack([rng.randint(0, n_ent, steps * B), rng.randint(0, n_rel, steps * B), rng.randint(0, n_ent, steps * B)], 1).astype(np.int32)
-neg = np.repeat(pos, k, 0)
-neg[:, 2] = rng.randint(0, n_ent, len(neg))
-offsets = (np.arange(steps + 1) * B).astype(np.int64)
-offsets[3] -= 37                                                  # ragged batches
-splits = np.full(steps, B // 2, np.int64)
 dev = torch.device("cuda:0")
-pos_d, neg_d = ops.to_ids(pos), ops.to_ids(neg)
-off_d, spl_d = torch.from_numpy(offsets).to(dev), torch.from_numpy(splits).to(dev)
-res = {}
-for mode in ("plain", "comm"):
-    for opt in ("Adagrad", "SGD"):
-        cfg = ops.make_step_cfg(loss="limited", loss_norm="L2", pos_margin=0.01, neg_margin=2.0, balance=0.2, optimizer=opt, lr=0.02,
-                                neg_group_k=k)
-        ent, rel = EmbeddingTable(ent_h, True, "e"), EmbeddingTable(rel_h, True, "r")
-        tr = TripleTrainer(ent, rel, cfg, opt)
-        tr.count_steps(steps)
-        if mode == "plain":
-            ops.triple_epoch(ent.var, tr.ent_acc, rel.var, tr.rel_acc, d, pos_d, offsets, splits, k, None, None, 1, 0, neg_d, None, tr.cfg,
-                             tr.ws, tr.loss, off_d, spl_d)
-            acc = tr.ent_acc
-        else:
-            comm = ops.comm_single_or_none()
-            bufs = ops.part_buffers(n_ent, n_rel, ent.ld, 1, dev, adagrad=opt == "Adagrad")
-            ops.triple_epoch_comm(comm, ent.var, bufs["acc_own"], rel.var, tr.rel_acc, d, pos_d, offsets, splits, k, None, None, 1, 0, neg_d,
-                                  None, tr.cfg, tr.ws, tr.loss, off_d, spl_d, bufs)
+for d in [int(x) for x in os.environ.get("OEA_DIMS", "40").split(",")]:     # (one process for all of them: the switches are read once)
+    rng = np.random.RandomState(7)
+    n_ent, n_rel, B, k, steps = 1003, 19, 900, 3, 5
+    ent_h = (rng.standard_normal((n_ent, d)) / np.sqrt(d)).astype(np.float32)
+    rel_h = (rng.standard_normal((n_rel, d)) / np.sqrt(d)).astype(np.float32)
+    pos = np.stack([rng.randint(0, n_ent, steps * B), rng.randint(0, n_rel, steps * B), rng.randint(0, n_ent, steps * B)], 1).astype(np.int32)
+    neg = np.repeat(pos, k, 0)
+    neg[:, 2] = rng.randint(0, n_ent, len(neg))
+    offsets = (np.arange(steps + 1) * B).astype(np.int64)
+    offsets[3] -= 37                                                  # ragged batches
+    splits = np.full(steps, B // 2, np.int64)
+    pos_d, neg_d = ops.to_ids(pos), ops.to_ids(neg)
+    off_d, spl_d = torch.from_numpy(offsets).to(dev), torch.from_numpy(splits).to(dev)
+    res = {}
+    for mode in ("plain", "comm"):
+        for opt in ("Adagrad", "SGD"):
+            cfg = ops.make_step_cfg(loss="limited", loss_norm="L2", pos_margin=0.01, neg_margin=2.0, balance=0.2, optimizer=opt, lr=0.02,
+                                    neg_group_k=k)
+            ent, rel = EmbeddingTable(ent_h, True, "e"), EmbeddingTable(rel_h, True, "r")
+            tr = TripleTrainer(ent, rel, cfg, opt)
+            tr.count_steps(steps)
+            if mode == "plain":
+                ops.triple_epoch(ent.var, tr.ent_acc, rel.var, tr.rel_acc, d, pos_d, offsets, splits, k, None, None, 1, 0, neg_d, None, tr.cfg,
+                                 tr.ws, tr.loss, off_d, spl_d)
+                acc = tr.ent_acc
+            else:
+                comm = ops.comm_single_or_none()
+                bufs = ops.part_buffers(n_ent, n_rel, ent.ld, 1, dev, adagrad=opt == "Adagrad")
+                ops.triple_epoch_comm(comm, ent.var, bufs["acc_own"], rel.var, tr.rel_acc, d, pos_d, offsets, splits, k, None, None, 1, 0, neg_d,
+                                      None, tr.cfg, tr.ws, tr.loss, off_d, spl_d, bufs)
+                torch.cuda.synchronize()
+                ops.check(ops.lib().oea_comm_destroy(comm))
+                acc = bufs["acc_own"]
             torch.cuda.synchronize()
-            ops.check(ops.lib().oea_comm_destroy(comm))
-            acc = bufs["acc_own"]
-        torch.cuda.synchronize()
-        res[mode + opt] = (ent.raw(), rel.raw(), None if acc is None else acc.cpu().numpy(), float(tr.loss.item()))
-for opt in ("Adagrad", "SGD"):
-    a, b = res["plain" + opt], res["comm" + opt]
-    for x, y, name in ((a[0], b[0], "entity table"), (a[1], b[1], "relation table"), (a[2], b[2], "accumulator")):
-        if x is None:
-            continue
-        err = float(np.abs(x - y).max() / max(np.abs(x).max(), 1e-30))
-        assert err <= 2e-6, (opt, name, err)
-    assert abs(a[3] - b[3]) <= 1e-6 * abs(a[3]), (opt, a[3], b[3])
-    assert float(np.abs(a[0] - ent_h).max()) > 1e-3               # the epoch did move the tables
+            res[mode + opt] = (ent.raw(), rel.raw(), None if acc is None else acc.cpu().numpy(), float(tr.loss.item()))
+    for opt in ("Adagrad", "SGD"):
+        a, b = res["plain" + opt], res["comm" + opt]
+        for x, y, name in ((a[0], b[0], "entity table"), (a[1], b[1], "relation table"), (a[2], b[2], "accumulator")):
+            if x is None:
+                continue
+            err = float(np.abs(x - y).max() / max(np.abs(x).max(), 1e-30))
+            assert err <= 2e-6, (d, opt, name, err)
+        assert abs(a[3] - b[3]) <= 1e-6 * abs(a[3]), (d, opt, a[3], b[3])
+        assert float(np.abs(a[0] - ent_h).max()) > 1e-3               # the epoch did move the tables
 print("EPOCH_COMM_OK")
 '''
 
@@ -208,6 +209,16 @@ def test_partitioned_epoch_from_one_c_call_single_rank():
     with 2 and 4 ranks through torch.distributed above)."""
     p = subprocess.run([sys.executable, "-c", EPOCH_COMM_WORKER], env=dict(os.environ, OEA_ROOT=ROOT), stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=300)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0 and "EPOCH_COMM_OK" in out, out[-3000:]
+
+
+def test_partitioned_epoch_single_rank_with_16_lane_groups():
+    """The same under OEA_APPLY_G16=1 at d = 24, 50, 75, 96, 100, 128 (2, 4, 5, 6, 7, 8 fragments of 16 lanes) and 200:
+    `part_apply_kernel<16, 2|4|5|6|7|8>` and `<64, 4>` at one rank against the plain epoch call, which takes `apply_rows<16, ...>`
+    (one rule for the group width, so the two round alike); the worker's bounds."""
+    env = dict(os.environ, OEA_ROOT=ROOT, OEA_APPLY_G16="1", OEA_DIMS="24,50,75,96,100,128,200")
+    p = subprocess.run([sys.executable, "-c", EPOCH_COMM_WORKER], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     out = p.stdout.decode(errors="replace")
     assert p.returncode == 0 and "EPOCH_COMM_OK" in out, out[-3000:]
 
@@ -280,7 +291,7 @@ from openea_amd.models.trainer import EmbeddingTable, RelationTripleEpochs, Trip
 from openea_amd.modules.load.synth import make_kgs
 kgs = make_kgs("small", mode="swapping", seed=0)
 rng = np.random.RandomState(2)
-d, k = 36, 4
+d, k = int(os.environ.get("OEA_DIM", "36")), 4
 ent_h = (rng.standard_normal((kgs.entities_num, d)) / np.sqrt(d)).astype(np.float32)
 rel_h = (rng.standard_normal((kgs.relations_num, d)) / np.sqrt(d)).astype(np.float32)
 opt = os.environ["OEA_OPT"]
@@ -326,13 +337,14 @@ if world > 1:
 '''
 
 
-def _launch_epochs(tmp_path, world, opt, det, exchange="step", chunk=0):
+def _launch_epochs(tmp_path, world, opt, det, exchange="step", chunk=0, **env_extra):
     # fixed point: five epochs with a neighbour refresh in between, compared BIT FOR BIT.  fp32 atomics: the single-GPU job is
     # not reproducible run to run (the order of the atomics), a flipped hinge or a neighbour set that differs by one entity
     # after the refresh grows into 5e-3 per row within three epochs -- two epochs without the refresh are held to 1e-4
     env = dict(os.environ, OEA_ROOT=ROOT, OEA_OUT=str(tmp_path), OEA_PORT=str(_free_port()), WORLD_SIZE=str(world), OEA_OPT=opt,
                OEA_STEP_DETERMINISTIC="1" if det else "0", OEA_EPOCHS="5" if det else "2", OEA_REFRESH="1" if det else "0",
                OEA_EXCHANGE=exchange, OEA_CHUNK=str(chunk))
+    env.update(env_extra)                                 # (e.g. OEA_EPOCHS / OEA_REFRESH other than the two defaults above)
     env.pop("OEA_DP_C_EPOCH", None)
     procs = [subprocess.Popen([sys.executable, "-c", EPOCH_RANKS_WORKER], env=dict(env, RANK=str(r)), stdout=subprocess.PIPE,
                               stderr=subprocess.STDOUT) for r in range(world)]
@@ -416,6 +428,24 @@ def test_boundary_row_exchange_with_2_and_4_ranks_equals_the_single_process_job(
         with capsys.disabled():
             print("halo exchange at world %d: %.0f bytes per step and rank (dense protocol: %.0f)" % (world, float(ranks[0]["xbytes"]), dense))
         assert float(ranks[0]["xbytes"]) < dense
+
+
+@pytest.mark.parametrize("d", [20, 68, 100])
+def test_owned_row_optimiser_with_16_lane_groups_equals_the_single_process_job(tmp_path, d):
+    """OEA_APPLY_G16=1 in the fixed-point build, Adagrad, two epochs without the refresh, d = 20, 68, 100 (2, 5, 7 fragments of 16
+    lanes): the single-process job runs `apply_rows<16, IT>`, the 2-rank job `part_apply_kernel<16, IT>` (dense exchange) and
+    `halo_apply_kernel<16, IT>` (boundary-row exchange).  One rule chooses the group width and with it the order of the row
+    reductions, so tables and loss are the single-process job's bit for bit, as in the fixed-point cases above."""
+    env = dict(OEA_APPLY_G16="1", OEA_DIM=str(d), OEA_EPOCHS="2", OEA_REFRESH="0")
+    single = _launch_epochs(tmp_path, 1, "Adagrad", True, **env)[0]
+    assert int(single["det"]) == 1 and int(single["ld"]) == (d + 3) // 4 * 4
+    for exchange in ("step", "halo"):
+        ranks = _launch_epochs(tmp_path, 2, "Adagrad", True, exchange=exchange, **env)
+        assert sum(int(r["n"]) for r in ranks) == int(single["n"])
+        for r in ranks:
+            assert np.array_equal(r["ent"], single["ent"]) and np.array_equal(r["rel"], single["rel"]), \
+                "d %d, %s exchange: the 2-rank job must equal the single-process job bit for bit" % (d, exchange)
+            assert float(r["loss"]) == float(single["loss"]), (d, exchange, float(r["loss"]), float(single["loss"]))
 
 
 @pytest.mark.parametrize("world,k", [(2, 4), (4, 10), (8, 10), (3, 0)])

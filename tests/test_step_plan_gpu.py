@@ -444,12 +444,14 @@ def edge_cases():
 
 ENVS = {"g0": dict(OEA_STEP_PLAN="2", OEA_APPLY_G16="0"),
         "g16": dict(OEA_STEP_PLAN="2", OEA_APPLY_G16="1"),
-        "g16-dword": dict(OEA_STEP_PLAN="2", OEA_APPLY_G16="1", OEA_APPLY_V4="0")}
+        "g16-dword": dict(OEA_STEP_PLAN="2", OEA_APPLY_G16="1", OEA_APPLY_V4="0"),
+        # the plan refused: the flag-driven optimiser with 16-lane groups (`apply_rows<16, 2|4|5|6|7|8>`; d 200: `apply_rows<64, 4>`)
+        "atomic-g16": dict(OEA_STEP_PLAN="0", OEA_APPLY_G16="1")}
 
 
 def env_cases(env):
     """what the worker process of a set of switches runs"""
-    cs = small_cases() + (edge_cases() if env != "g16-dword" else [])
+    cs = small_cases() + (edge_cases() if env in ("g0", "g16") else [])
     if env == "g0":
         cs.append(case("ranges", d=75, k=5, neg_margin=2.0, seed=501, calls=[(0, 2), (2, 4)]))
     return cs
@@ -460,7 +462,9 @@ def test_every_instance_and_the_grid_stride_edges(env, tmp_path, capsys):
     """OEA_STEP_PLAN=2 (the plan whatever the table size) with 32-lane groups (`apply_step_plan<32, 1..4>`, `<64, 4>`), 16-lane groups
     and float4 rows (`apply_step_plan_v4<16, 2|4|5|6|7|8>`), 16-lane groups and dword fragments (`apply_step_plan<16, ...>`):
     small_cases() on 6,000 entities in batches of 3,000 / 0 (empty) / 2,500 / 64, teacher-forced; in the first two also
-    edge_cases(), where a grid-stride loop of the optimiser kernel runs more than once."""
+    edge_cases(), where a grid-stride loop of the optimiser kernel runs more than once.
+    "atomic-g16": OEA_STEP_PLAN=0 with 16-lane groups -- no plan, every gradient through the atomic scratch and the flag-driven
+    `apply_rows<16, 2|4|5|6|7|8>` (`<64, 4>` at d 200), held to the same oracle steps with the same checks and left-out caps."""
     cases = env_cases(env)
     with capsys.disabled():
         print()
@@ -468,11 +472,13 @@ def test_every_instance_and_the_grid_stride_edges(env, tmp_path, capsys):
         for ci, c in enumerate(cases):
             if c["calls"] is not None:                               # test_step_ranges_across_calls
                 continue
-            assert bool(out["%d_supported" % ci]), c["name"]
+            assert bool(out["%d_supported" % ci]) == (env != "atomic-g16"), c["name"]
             tag = "%s %s" % (env, c["name"])
             expect = ("outside", "listed", "hubs", "merge", "scan")
             if c["neg_margin"] == 2.0:
                 expect = ("outside", "listed", "hubs")
+            if env == "atomic-g16":
+                expect = ()                                          # (no plan: none of its branches runs)
             counts, traj = check_case(tag, c, factory(ci), expect)
             if c["name"] == "stride-plan":
                 groups = PLAN_BLOCKS * (16 if env != "g0" else 8)
