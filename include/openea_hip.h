@@ -366,6 +366,40 @@ int oea_proje_step(const oea_proje_vars *vars, int64_t n_ent, int64_t n_rel, int
                    const int32_t *sampled, const float *log_q_sampled, int64_t n_sampled, const int64_t *num_tries, int64_t t, float lr,
                    void *workspace, int64_t max_pos, int64_t max_sampled, double *loss_accum, int32_t phase, void *stream);
 
+/* ---- ConvE (models/neural/conve.py) --------------------------------------------------------------------------------------------
+ * oea_conve_step: forward pass, gradients and TF's dense Adam of one ConvE batch (csrc/conve_step.hip): the head and the relation
+ * row, normalised, stacked into a [2x, y] image (x y = dim, x = the largest divisor of dim below sqrt(dim) + 1), batch norm,
+ * dropout, a 3 x 3 'same' convolution into filter_num channels, batch norm, relu, dropout, a dense relu layer back to dim, batch
+ * norm, and ProjE's sampled softmax.  The three batch norms are the affine map v gamma / sqrt(1 + 1e-3) + beta (inference mode on
+ * the initial moving statistics).  The fourteen variables with their Adam moments, in this order: ent_embeds [n_ent, ld],
+ * rel_embeds [n_rel, ld], entity_w [n_ent, ld], entity_b [n_ent], gamma1, beta1 [y], kern [3, 3, 1, F] (tap-major: (di 3 + dj) F
+ * + f), cbias, gamma2, beta2 [F], fcW [2 dim F, ld] (row f 2 dim + image position; the pad columns stay zero), fcb, gamma3, beta3
+ * [dim].  pos / sampled / log_q_sampled / num_tries, phase, workspace, loss_accum and t as for oea_proje_step;
+ * oea_conve_grads gives the fourteen dense fp32 gradients after OEA_PHASE_GRAD.
+ * Dropout: element e of layer L (0: the 2 dim inputs of the convolution, 1: the 2 dim F inputs of the dense layer, in the order
+ * of fcW's rows) of batch row b at step mask_step is kept iff lane e & 7 of Philox4x32-10(counter = (e >> 3, 0x436f6e00 | L, b,
+ * mask_step mod 2^32), key = (seed lo, seed hi)) is below floor(keep_prob 65536); lane l is the low (l even) or high (l odd) 16
+ * bits of word l >> 1.  A kept element is multiplied by 1 / keep_prob.  keep_prob == 1 draws nothing and masks nothing.  The mask
+ * does not depend on the batch size or on any tiling.
+ * dim > 128, filter_num > 64: OEA_EUNSUPPORTED; keep_prob outside (0, 1], filter_num < 1, ld % 4 != 0, n_sampled < 2, n_pos < 1
+ * or > max_pos, a null pointer: OEA_EINVAL -- both before anything is launched.  ids are not checked on the device.  One GPU. */
+typedef struct oea_conve_vars {
+    float *p[14], *m[14], *v[14];
+} oea_conve_vars;
+typedef struct oea_conve_cfg {
+    int32_t filter_num;
+    float keep_prob;
+    uint64_t seed;
+} oea_conve_cfg;
+size_t oea_conve_workspace_floats(int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld, int32_t filter_num, int64_t max_pos,
+                                  int64_t max_sampled);
+int oea_conve_grads(void *workspace, int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld, int32_t filter_num, int64_t max_pos,
+                    int64_t max_sampled, void **grads);
+int oea_conve_step(const oea_conve_vars *vars, const oea_conve_cfg *cfg, int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld,
+                   const int32_t *pos, int64_t n_pos, const int32_t *sampled, const float *log_q_sampled, int64_t n_sampled,
+                   const int64_t *num_tries, uint64_t mask_step, int64_t t, float lr, void *workspace, int64_t max_pos,
+                   int64_t max_sampled, double *loss_accum, int32_t phase, void *stream);
+
 /* ---- IPTransE (approaches/iptranse.py) -----------------------------------------------------------------------------------------
  * The path half of train_loss (_generate_path_loss, iptranse.py:173-177, scaled by args.path_parm at iptranse.py:179-181):
  *   path_parm * sum_p (1 / w_p) relu(|x + y - r|^2 + margin - |x + y - r'|^2),  x, y, r, r' rows of Rn = l2n(rel) (rel itself when

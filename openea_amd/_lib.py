@@ -95,6 +95,16 @@ class ProjEVars(C.Structure):
     _fields_ = [("p", C.c_void_p * 8), ("m", C.c_void_p * 8), ("v", C.c_void_p * 8)]
 
 
+class ConvEVars(C.Structure):
+    """mirror of `oea_conve_vars` (include/openea_hip.h): the fourteen variables, their Adam m and v."""
+    _fields_ = [("p", C.c_void_p * 14), ("m", C.c_void_p * 14), ("v", C.c_void_p * 14)]
+
+
+class ConvECfg(C.Structure):
+    """mirror of `oea_conve_cfg` (include/openea_hip.h)."""
+    _fields_ = [("filter_num", C.c_int32), ("keep_prob", C.c_float), ("seed", C.c_uint64)]
+
+
 LOSS_KIND = {"margin-based": 0, "limited": 1, "logistic": 2, "positive": 3, "align": 4}
 OPT_KIND = {"SGD": 0, "Adagrad": 1, "Adam": 2, "Adadelta": 3}
 METRIC = {"inner": 0, "manhattan": 1, "euclidean": 2, "manhattan_f32": 3}
@@ -185,6 +195,10 @@ PROTOTYPES = {
     "oea_proje_grads": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i64, _i64, C.POINTER(C.c_void_p)]),
     "oea_proje_step": (C.c_int, [C.POINTER(ProjEVars), _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64,
                                  _i64, _vp, _i32, _vp]),
+    "oea_conve_workspace_floats": (_sz, [_i64, _i64, _i32, _i32, _i32, _i64, _i64]),
+    "oea_conve_grads": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, C.POINTER(C.c_void_p)]),
+    "oea_conve_step": (C.c_int, [C.POINTER(ConvEVars), C.POINTER(ConvECfg), _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp,
+                                 _u64, _i64, _f32, _vp, _i64, _i64, _vp, _i32, _vp]),
     "oea_path_workspace_bytes": (_sz, [_i64, _i32]),
     "oea_path_grad": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "oea_ptranse_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _f32,

@@ -5,6 +5,7 @@ current HIP stream and ``torch.distributed``.  All arithmetic happens inside
 libopenea_hip.so; nothing in this module computes on the CPU.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -385,6 +386,79 @@ def proje_step(variables, moments_m, moments_v, dim, pos, sampled, log_q, num_tr
     check(lib().oea_proje_step(C.byref(v), n_ent, n_rel, dim, ld, _p(pos), pos.shape[0], _p(sampled), _p(log_q), sampled.numel(),
                                _p(num_tries), int(t), float(lr), _p(workspace), max_pos, max_s, _p(loss_accum), int(phase),
                                _stream()))
+
+
+# ---- ConvE -------------------------------------------------------------------------------------------------------
+CONVE_MAX_FILTERS = 64
+CONVE_VARS = ("ent_embeds", "rel_embeds", "entity_w", "entity_b", "gamma1", "beta1", "kern", "cbias", "gamma2", "beta2", "fcW", "fcb",
+              "gamma3", "beta3")
+
+
+def dim_factorization(d):
+    """conve.py:10-18 without the print: (x, y), x the largest divisor of d below sqrt(d) + 1, y = d // x"""
+    half = int(math.sqrt(d)) + 1
+    while d % half > 0:
+        half -= 1
+    return half, d // half
+
+
+def _conve_shapes(n_ent, n_rel, dim, ld, filters):
+    y = dim_factorization(dim)[1]
+    return [(n_ent, ld), (n_rel, ld), (n_ent, ld), (n_ent,), (y,), (y,), (9 * filters,), (filters,), (filters,), (filters,),
+            (2 * dim * filters, ld), (dim,), (dim,), (dim,)]
+
+
+def conve_workspace(n_ent, n_rel, dim, ld, filters, max_pos, max_sampled, dev=None):
+    """workspace of conve_step for batches of up to max_pos positives and max_sampled candidates (zeroed once)"""
+    shape = (int(n_ent), int(n_rel), int(dim), int(ld), int(filters), int(max_pos), int(max_sampled))
+    n = lib().oea_conve_workspace_floats(*shape)
+    if n == 0:
+        # the shape is refused: the accessor says why
+        check(lib().oea_conve_grads(None, *shape, None))
+    ws = torch.zeros(n, dtype=torch.float32, device=dev or device())
+    ws._conve_shape = shape
+    return ws
+
+
+def conve_grads(workspace):
+    """the fourteen dense fp32 gradients a PHASE_GRAD call left in the workspace, as views (order: CONVE_VARS; kern as [9 F],
+    tap-major, which is [3, 3, 1, F] flattened)"""
+    n_ent, n_rel, dim, ld, filters, max_pos, max_s = workspace._conve_shape
+    ptrs = (C.c_void_p * 14)()
+    check(lib().oea_conve_grads(_p(workspace), n_ent, n_rel, dim, ld, filters, max_pos, max_s, ptrs))
+    base = workspace.data_ptr()
+    out = []
+    for ptr, shp in zip(ptrs, _conve_shapes(n_ent, n_rel, dim, ld, filters)):
+        off = (ptr - base) // 4
+        out.append(workspace[off:off + int(np.prod(shp))].view(*shp))
+    return out
+
+
+def conve_step(variables, moments_m, moments_v, dim, filters, keep_prob, seed, pos, sampled, log_q, num_tries, mask_step, t, lr,
+               workspace, loss_accum, phase=PHASE_BOTH, check_ids=True):
+    """One ConvE step in place (oea_conve_step).  variables / moments_m / moments_v: fourteen device fp32 tensors each in the order
+    of CONVE_VARS (tables [n, ld], fcW [2 dim F, ld], kern [9 F] or [3, 3, 1, F]); pos int32 [n, 3]; sampled, log_q, num_tries as
+    LogUniformSampler.sample returned them; (seed, mask_step) select the dropout masks.  check_ids: refuse ids outside the tables
+    here (the kernels do not look)."""
+    n_ent, n_rel, wdim, ld, wf, max_pos, max_s = workspace._conve_shape
+    assert len(variables) == len(moments_m) == len(moments_v) == 14 and wdim == dim and wf == filters
+    if dim <= PROJE_MAX_DIM and 1 <= filters <= CONVE_MAX_FILTERS:
+        for x, shp in zip(variables, _conve_shapes(n_ent, n_rel, dim, ld, filters)):
+            assert x.numel() == int(np.prod(shp)) and (len(shp) == 1 or tuple(x.shape) == shp), (tuple(x.shape), shp)
+    if check_ids and pos.numel():
+        hi = pos.max(dim=0).values.tolist()
+        lo = int(pos.min())
+        if lo < 0 or hi[0] >= n_ent or hi[1] >= n_rel or hi[2] >= n_ent or int(sampled.max()) >= n_ent or int(sampled.min()) < 0:
+            raise OpenEAHipError("conve_step: an id lies outside its table (entities %d, relations %d)" % (n_ent, n_rel))
+    v = _lib.ConvEVars()
+    for i in range(14):
+        v.p[i], v.m[i], v.v[i] = variables[i].data_ptr(), moments_m[i].data_ptr(), moments_v[i].data_ptr()
+    for x in list(variables) + list(moments_m) + list(moments_v):
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+    cfg = _lib.ConvECfg(int(filters), float(keep_prob), int(seed) & (2 ** 64 - 1))
+    check(lib().oea_conve_step(C.byref(v), C.byref(cfg), n_ent, n_rel, dim, ld, _p(pos), pos.shape[0], _p(sampled), _p(log_q),
+                               sampled.numel(), _p(num_tries), int(mask_step) & (2 ** 64 - 1), int(t), float(lr), _p(workspace), max_pos,
+                               max_s, _p(loss_accum), int(phase), _stream()))
 
 
 # ---- IPTransE ---------------------------------------------------------------------------------------------------
