@@ -1569,7 +1569,10 @@ void gather_packed_rows(const float *qp, int kp, const int32_t *rows, const int3
 
 // ---- short candidate lists: the k best of a row of at most 1,024 values by RANKING (no sort) ---------------------------------------------
 // One wave per row; every lane owns the columns lane, lane + 64, ...; rank of a value = how many values of the row beat it (better
-// value, or the same value in an earlier column); rank < k selects.  The selected columns leave in ascending column order (a wave
+// value, or the same value in an earlier column); rank < k selects.  NaN has a place in that order -- last in BOTH directions, NaNs
+// among themselves by column (numpy's sort order) -- so "beats" is a strict total order of the columns, the ranks are a permutation
+// of 0..nc-1 and exactly k columns have rank < k: a row never stores past its k slots (with every comparison against NaN false, all
+// m NaNs of a row had rank 0 and the row selected m + min(k, rest) columns).  The selected columns leave in ascending column order (a wave
 // ballot prefix), optionally mapped through the row's id list; the k-th best value (rank k - 1) is written beside them.  Replaces
 // torch.argsort / sort / topk on [rows, k + margin] matrices (approaches/rdgcn.py:get_neg, ops.l1_grid_topk_means).
 template <typename T, bool LARGEST>
@@ -1596,8 +1599,9 @@ __global__ __launch_bounds__(256) void row_rank_select_kernel(const T *__restric
             const int c = lane + 64 * u;
             if (c < nc) {
                 const T x = mine[c];
-                const bool beats = LARGEST ? (o > x) : (o < x);
-                rank[u] += (beats || (o == x && j < c)) ? 1 : 0;
+                const bool o_nan = o != o, x_nan = x != x;
+                const bool beats = (LARGEST ? (o > x) : (o < x)) || (x_nan && !o_nan);
+                rank[u] += (beats || ((o == x || (o_nan && x_nan)) && j < c)) ? 1 : 0;
             }
         }
     }

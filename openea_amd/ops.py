@@ -1006,7 +1006,9 @@ class L1Grid:
         self.step = max(hi - lo, 1e-30) / 65535.0
         self.q1 = quantize_rows_u16(e1, dim, lo, 1.0 / self.step)
         self.q2 = self.q1 if e2 is e1 else quantize_rows_u16(e2, dim, lo, 1.0 / self.step)
-        self.err = (dim * 1.02 + 1.0) * self.step      # half a step per operand and column, + the fp32 rounding of the grid map
+        # per entry 0.5 step (rintf) + 2 * 65535 * 2^-24 (fp32 roundings of inv_step and of x - lo) + 2^-9 (of the product, < 65536)
+        # = 0.5098 steps, two entries per column: 1.0196 dim steps (pressed to 0.98 dim by tests/test_l1_grid_gpu.py)
+        self.err = (dim * 1.02 + 1.0) * self.step
         self.ld = (e2.shape[0] + 31) // 32 * 32
         self.rows_per = int(max(128, min(e1.shape[0], block_bytes // (4 * self.ld))))
         self.strips = {}                               # r0 -> strip of query rows [r0, r0 + rows) against all of e2
