@@ -329,6 +329,80 @@ enum { OEA_SEMANTIC_HOLE = 0, OEA_SEMANTIC_SIMPLE = 1, OEA_SEMANTIC_DISTMULT = 2
 int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel,
                       int32_t dim, int32_t ld, const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg,
                       const oea_step_cfg *cfg, void *step_workspace, double *loss_accum, void *stream);
+/* JAPE's triple step (approaches/jape.py:59-84), one wave per positive and its k = cfg->neg_group_k negatives as above:
+ *   u = l2n?(ent)[e], w = l2n?(rel)[r] (by cfg->ent_l2_norm / rel_l2_norm), score = |uh + w - ut|^2,
+ *   loss = sum_pos score - neg_alpha sum_neg score   (a negative weight on the negatives and no hinge: none of OEA_LOSS_*).
+ * neg, cfg, step_workspace and the closing oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY) as for oea_semantic_step.
+ * Adam / Adadelta, dim > 128: OEA_EUNSUPPORTED; n_neg != k n_pos, ld % 4 != 0, neg_alpha < 0 or NaN: OEA_EINVAL -- both before
+ * anything is launched.  loss_accum += the batch SUM (it may be negative). */
+int oea_jape_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim, int32_t ld,
+                  const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg, float neg_alpha, const oea_step_cfg *cfg,
+                  void *step_workspace, double *loss_accum, void *stream);
+/* m distinct elements of [0, n) (random.sample(range(n), m), attr2vec.py:150 / jape.py:134): out[i] = pi(i), i < m, with pi a
+ * bijection of [0, n) that is a pure function of (seed, step) -- a 6-round Feistel network over max(2, ceil(log2 n)) bits, cycle
+ * walked into [0, n), its round keys from Philox4x32-10(counter = (step lo, step hi, 0x64697374, 0 | 1), key = (seed lo, seed hi))
+ * (csrc/sample_distinct.hip).  out: device int32 [m].  One launch, no host read.  n < 1, n >= 2^31, m > n: OEA_EINVAL. */
+int oea_sample_distinct(int64_t n, int64_t m, uint64_t seed, uint64_t step, int32_t *out, void *stream);
+/* JAPE's thresholded attribute similarity as a CSR (jape.py:147-149: sim_mat[sim_mat < threshold] = 0), never dense beyond one block
+ * of rows: for row blocks of block_rows rows of e1, oea_sim_matrix(OEA_METRIC_INNER) into block_buf (block_rows * n2 floats), and the
+ * entries >= threshold are kept.  oea_sim_csr_count writes indptr int64 [n1 + 1] (indptr[n1] = nnz, which the caller reads back to
+ * allocate); oea_sim_csr_fill, with the same arguments and that indptr, writes col int32 [nnz] (ascending within a row) and val
+ * fp32 [nnz] (both at least one element long), and adds to *mismatch (device int32, zeroed by the caller) the number of rows
+ * that kept another number of entries than oea_sim_csr_count found: 0 as long as oea_sim_matrix repeats its bits.  A null pointer, n1 < 1, n2 < 1, ld % 4 != 0, a NaN threshold: OEA_EINVAL before any launch. */
+int oea_sim_csr_count(const float *e1, int64_t n1, int32_t ld1, const float *e2, int64_t n2, int32_t ld2, int32_t dim, float threshold,
+                      int64_t block_rows, float *block_buf, int64_t *indptr, void *stream);
+int oea_sim_csr_fill(const float *e1, int64_t n1, int32_t ld1, const float *e2, int64_t n2, int32_t ld2, int32_t dim, float threshold,
+                     int64_t block_rows, float *block_buf, const int64_t *indptr, int32_t *col, float *val, int32_t *mismatch,
+                     void *stream);
+/* JAPE's similarity loss (jape.py:86-95) over that CSR, for the m sampled positions rows[i] into ref1 (one wave per row, fp64):
+ *   t = sum_j val_ij l2n(ent)[ref2_ids[col_ij]],   loss_accum += beta sum_i | l2n(ent)[ref1_ids[rows[i]]] - l2n(t) |^2,
+ * l2n(v) = v / sqrt(max(|v|^2, 1e-12)), so an empty row gives l2n(0) = 0.  Nothing but loss_accum is written: the reference builds
+ * sim_optimizer and never runs it (jape.py:136 fetches self.sim_loss alone).  col / val: non-null also for an empty matrix (they
+ * are then not read).  dim > 128: OEA_EUNSUPPORTED; ld % 4 != 0, a null pointer: OEA_EINVAL -- before any launch.  ids are not checked on the device. */
+int oea_jape_sim_loss(const float *ent, int64_t n_ent, int32_t dim, int32_t ld, const int32_t *ref1_ids, int64_t n_ref1,
+                      const int32_t *ref2_ids, int64_t n_ref2, const int64_t *indptr, const int32_t *col, const float *val,
+                      const int32_t *rows, int64_t m, float beta, double *loss_accum, void *stream);
+/* The candidate sets of n_steps steps in ONE launch, for the steps that are too short to wait for oea_log_uniform_sample's status
+ * word (declared with ProjE below; the values here are its values bit for bit): workgroup s writes out_ids[s, :], out_num_tries[s],
+ * out_log_q_sampled[s, :] of step step0 + s, and status[s] = 0, or 1 when n_sampled distinct classes did not appear in 64 n_sampled
+ * draws (that step's ids are then 0 .. n_sampled - 1 with log Q 0: in bounds, not a sample); the caller reads status once per
+ * epoch.  The first-appearance table lives in LDS: n_classes > OEA_LOG_UNIFORM_STEPS_MAX_CLASSES is OEA_EUNSUPPORTED before any
+ * launch; n_sampled < 1, n_sampled > n_classes, a null pointer: OEA_EINVAL. */
+#define OEA_LOG_UNIFORM_STEPS_MAX_CLASSES 8192
+int oea_log_uniform_sample_steps(int64_t n_classes, int64_t n_sampled, uint64_t seed, uint64_t step0, int64_t n_steps,
+                                 const double *thresholds, int32_t *out_ids, int64_t *out_num_tries, float *out_log_q_sampled,
+                                 int32_t *status, void *stream);
+/* Attr2Vec's step (approaches/attr2vec.py:106-124): a skip-gram over attribute pairs under tf.nn.nce_loss and Adagrad.
+ *   x_b = l2n(embeds)[in_b], w_c = l2n(nce_weights)[c]; true_b = x_b . w_lab + bias[lab] - log Q(lab), samp_bj = x_b . w_sj + bias[s_j]
+ *   - log Q(s_j); loss = mean_b (softplus(-true_b) + sum_j softplus(samp_bj)); log Q as for ProjE (num_true = 1, accidental hits
+ *   kept, range_max = n_attr, the labels' at *num_tries).
+ * pairs int32 [n_batch, 2] = (input, label); sampled / log_q_sampled [n_sampled] and num_tries as the samplers write them.  The
+ * sampled half runs over DISTINCT inputs x candidates, weighted by an input's multiplicity (csrc/attr2vec_step.hip).  phase:
+ * OEA_PHASE_GRAD leaves the gradients w.r.t. embeds [n_attr, ld], nce_weights [n_attr, ld], nce_biases [n_attr] (dense fp32, rows
+ * the batch did not touch zero) readable through oea_attr2vec_grads; OEA_PHASE_APPLY runs Adagrad (acc += g^2, v -= lr g /
+ * sqrt(acc); accumulators start at 0.1) on the rows that received gradient, all others keep their bits.  workspace:
+ * oea_attr2vec_workspace_bytes(n_attr, ld, max_sampled) bytes, zeroed once, n_sampled <= max_sampled.  loss_accum += the batch
+ * MEAN.  OEA_PHASE_APPLY reads neither the batch nor the candidates: pairs, sampled, log_q_sampled, num_tries may be NULL and
+ * n_batch, n_sampled anything there.  dim > 128: OEA_EUNSUPPORTED; ld % 4 != 0, and outside OEA_PHASE_APPLY n_batch < 1, n_sampled
+ * < 1 or > n_attr or > max_sampled, a null pointer: OEA_EINVAL -- both before anything is launched.  ids are not checked on the device.  One GPU.
+ * oea_attr2vec_epoch: `steps` steps over the device list pairs [n_pairs, 2] in one call with no host round trip: the candidates of
+ * all steps by oea_log_uniform_sample_steps(seed, step0) into cand_* ([steps, n_sampled], [steps], [steps, n_sampled], status
+ * [steps], which the caller reads afterwards), then per step batch_idx [n_batch] = oea_sample_distinct(n_pairs, n_batch, seed,
+ * step0 + s) and the step on pairs[batch_idx].  A step whose status word is not 0 changes nothing (its kernels return at once),
+ * so when the caller finds a failed draw the tables hold the other steps' updates only.  steps == 0 does nothing, whatever
+ * n_pairs is.  n_attr > OEA_LOG_UNIFORM_STEPS_MAX_CLASSES: OEA_EUNSUPPORTED. */
+typedef struct oea_attr2vec_vars {
+    float *embeds, *embeds_acc, *nce_weights, *nce_weights_acc, *nce_biases, *nce_biases_acc;
+} oea_attr2vec_vars;
+size_t oea_attr2vec_workspace_bytes(int64_t n_attr, int32_t ld, int64_t max_sampled);
+int oea_attr2vec_grads(void *workspace, int64_t n_attr, int32_t ld, int64_t max_sampled, void **grads);
+int oea_attr2vec_step(const oea_attr2vec_vars *vars, int64_t n_attr, int32_t dim, int32_t ld, const int32_t *pairs, int64_t n_batch,
+                      const int32_t *sampled, int64_t n_sampled, const float *log_q_sampled, const int64_t *num_tries, float lr,
+                      void *workspace, int64_t max_sampled, double *loss_accum, int32_t phase, void *stream);
+int oea_attr2vec_epoch(const oea_attr2vec_vars *vars, int64_t n_attr, int32_t dim, int32_t ld, const int32_t *pairs, int64_t n_pairs,
+                       int64_t n_batch, int32_t steps, uint64_t seed, uint64_t step0, const double *thresholds, int64_t n_sampled,
+                       int32_t *cand_ids, int64_t *cand_tries, float *cand_log_q, int32_t *cand_status, int32_t *batch_idx, float lr,
+                       void *workspace, int64_t max_sampled, double *loss_accum, void *stream);
 /* addresses of the entity gradient scratch and its touched flags inside a step workspace */
 int oea_step_entity_scratch(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, void **ent_grad,
                             void **ent_touched);

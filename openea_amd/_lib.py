@@ -95,6 +95,11 @@ class ProjEVars(C.Structure):
     _fields_ = [("p", C.c_void_p * 8), ("m", C.c_void_p * 8), ("v", C.c_void_p * 8)]
 
 
+class Attr2VecVars(C.Structure):
+    """mirror of `oea_attr2vec_vars` (include/openea_hip.h): the three variables, each followed by its Adagrad accumulator."""
+    _fields_ = [(n, C.c_void_p) for n in ("embeds", "embeds_acc", "nce_weights", "nce_weights_acc", "nce_biases", "nce_biases_acc")]
+
+
 class ConvEVars(C.Structure):
     """mirror of `oea_conve_vars` (include/openea_hip.h): the fourteen variables, their Adam m and v."""
     _fields_ = [("p", C.c_void_p * 14), ("m", C.c_void_p * 14), ("v", C.c_void_p * 14)]
@@ -189,6 +194,18 @@ PROTOTYPES = {
                                   _vp, _vp, _vp, _vp]),
     "oea_semantic_step": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
                                     _vp, _vp, _vp]),
+    "oea_jape_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _f32, C.POINTER(StepCfg), _vp, _vp, _vp]),
+    "oea_sample_distinct": (C.c_int, [_i64, _i64, _u64, _u64, _vp, _vp]),
+    "oea_sim_csr_count": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _f32, _i64, _vp, _vp, _vp]),
+    "oea_sim_csr_fill": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "oea_jape_sim_loss": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp]),
+    "oea_log_uniform_sample_steps": (C.c_int, [_i64, _i64, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "oea_attr2vec_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "oea_attr2vec_grads": (C.c_int, [_vp, _i64, _i32, _i64, C.POINTER(C.c_void_p)]),
+    "oea_attr2vec_step": (C.c_int, [C.POINTER(Attr2VecVars), _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i32,
+                                    _vp]),
+    "oea_attr2vec_epoch": (C.c_int, [C.POINTER(Attr2VecVars), _i64, _i32, _i32, _vp, _i64, _i64, _i32, _u64, _u64, _vp, _i64, _vp, _vp, _vp,
+                                     _vp, _vp, _f32, _vp, _i64, _vp, _vp]),
     "oea_log_uniform_workspace_bytes": (_sz, [_i64, _i64]),
     "oea_log_uniform_sample": (C.c_int, [_i64, _i64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "oea_proje_workspace_floats": (_sz, [_i64, _i64, _i32, _i32, _i64, _i64]),

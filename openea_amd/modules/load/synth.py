@@ -24,6 +24,16 @@ SHAPES = {
 }
 
 
+# name -> ((#att1, #att2), (#attribute triples1, #attribute triples2)); SURVEY Appendix B for the two benchmark shapes
+ATTRIBUTES = {
+    "EN-FR-15K-V1": ((308, 404), (73121, 67167)),
+    "EN-FR-100K-V1": ((466, 519), (497729, 426672)),
+    "tiny": ((24, 30), (1600, 1500)),
+    "small": ((40, 48), (14000, 13000)),
+}
+N_PROFILES = 32
+
+
 def _zipf_choice(rng, n, size, a=0.9):
     """indices in [0,n) with P(i) ~ (i+1)^-a (hubs at low indices)."""
     w = 1.0 / np.power(np.arange(1, n + 1, dtype=np.float64), a)
@@ -61,10 +71,44 @@ def generate_uri_dataset(shape="EN-FR-15K-V1", seed=0):
     return tri1, tri2, links[:n_train], links[n_train:n_train + n_valid], links[n_train + n_valid:]
 
 
-def make_kgs(shape="EN-FR-15K-V1", mode="mapping", ordered=True, seed=0, verbose=False):
-    """-> KGs built through the same id-assignment code as a real dataset."""
+def _attribute_triples(rng, prefix, profile, n_att, n_tri):
+    """n_tri (entity, attribute, value) triples over n_att attributes: entity i holds n_tri / n_ent distinct attributes (rounded so
+    that the total is exact) drawn without replacement under the weights of its latent profile -- a Zipf law over a
+    profile-specific order of the KG's attributes, so that two entities of one profile share most of theirs"""
+    n_ent = len(profile)
+    counts = np.full(n_ent, n_tri // n_ent, np.int64)
+    counts[rng.permutation(n_ent)[:n_tri - counts.sum()]] += 1
+    counts = np.minimum(counts, n_att)
+    logw = -1.5 * np.log(np.arange(1, n_att + 1, dtype=np.float64))
+    order = np.stack([rng.permutation(n_att) for _ in range(N_PROFILES)])           # rank of attribute a under profile p
+    out = set()
+    for lo in range(0, n_ent, 8192):
+        hi = min(lo + 8192, n_ent)
+        score = logw[order[profile[lo:hi]]] + rng.gumbel(size=(hi - lo, n_att))     # Gumbel top-k = weighted sampling without replacement
+        pick = np.argsort(-score, axis=1)
+        for i in range(lo, hi):
+            for a in pick[i - lo, :counts[i]]:
+                out.add(("%s/e%d" % (prefix, i), "%s/a%d" % (prefix, a), "v%d" % ((i * 31 + int(a)) % 97)))
+    return out
+
+
+def generate_attribute_triples(shape="EN-FR-15K-V1", seed=0):
+    """-> (attribute triples of KG1, of KG2) as URI triples.  Entity i of KG1 and entity i of KG2 (aligned) share one latent profile;
+    each KG maps a profile to its own attributes, so attribute co-occurrence across the training links carries the signal JAPE's
+    Attr2Vec reads.  A stream of its own: the relation triples and links of generate_uri_dataset do not change."""
+    n_ent = SHAPES[shape][0]
+    (a1, a2), (t1, t2) = ATTRIBUTES[shape]
+    rng = np.random.RandomState([seed, 0xa77])
+    profile = rng.randint(0, N_PROFILES, n_ent)
+    return _attribute_triples(rng, "kg1", profile, a1, t1), _attribute_triples(rng, "kg2", profile, a2, t2)
+
+
+def make_kgs(shape="EN-FR-15K-V1", mode="mapping", ordered=True, seed=0, verbose=False, attributes=False):
+    """-> KGs built through the same id-assignment code as a real dataset.  attributes=True adds generate_attribute_triples (for
+    the shapes in ATTRIBUTES); the default has none, as before."""
     tri1, tri2, train, valid, test = generate_uri_dataset(shape, seed)
-    return KGs(KG(tri1, set(), verbose=verbose), KG(tri2, set(), verbose=verbose), train, test, valid_links=valid,
+    att1, att2 = generate_attribute_triples(shape, seed) if attributes else (set(), set())
+    return KGs(KG(tri1, att1, verbose=verbose), KG(tri2, att2, verbose=verbose), train, test, valid_links=valid,
                mode=mode, ordered=ordered, verbose=verbose)
 
 

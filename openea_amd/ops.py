@@ -307,6 +307,142 @@ def semantic_step(model, ent, ent_acc, rel, rel_acc, dim, pos, neg, cfg, workspa
                                   _p(loss_accum), _stream()))
 
 
+# ---- JAPE -------------------------------------------------------------------------------------------------------
+JAPE_MAX_DIM = 128
+
+
+def jape_step(ent, ent_acc, rel, rel_acc, dim, pos, neg, neg_alpha, cfg, workspace, loss_accum):
+    """One JAPE triple step in place (oea_jape_step): loss = sum_pos |h + r - t|^2 - neg_alpha sum_neg |h + r - t|^2 on the rows
+    normalised by cfg's flags; neg [n * k, 3] with neg[p*k:(p+1)*k] the corruptions of pos p, k = cfg.neg_group_k; the batch
+    SUM is added to `loss_accum`."""
+    n_neg = 0 if neg is None else neg.shape[0]
+    check(lib().oea_jape_step(_p(ent), _p(ent_acc), ent.shape[0], _p(rel), _p(rel_acc), rel.shape[0], dim, ent.shape[1], _p(pos),
+                              pos.shape[0], _p(neg), n_neg, float(neg_alpha), C.byref(cfg), _p(workspace), _p(loss_accum),
+                              _stream()))
+
+
+def sample_distinct(n, m, seed, step, out=None, dev=None):
+    """m distinct elements of [0, n) as a pure function of (seed, step) (oea_sample_distinct) -> device int32 [m]"""
+    if out is None:
+        out = torch.empty(max(int(m), 0), dtype=torch.int32, device=dev or device())
+    assert out.dtype == torch.int32 and out.numel() >= m
+    check(lib().oea_sample_distinct(int(n), int(m), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _p(out), _stream()))
+    return out[:m]
+
+
+def sim_csr(e1, e2, dim, threshold, block_rows=4096):
+    """The entries >= threshold of e1 . e2^T as a CSR -> (indptr int64 [n1 + 1], col int32 [nnz] ascending within a row, val fp32
+    [nnz]); the dense matrix exists one block of `block_rows` rows at a time (oea_sim_csr_count / oea_sim_csr_fill).  Reads nnz
+    back once."""
+    n1, n2 = e1.shape[0], e2.shape[0]
+    block_rows = max(1, min(int(block_rows), n1))
+    buf = torch.empty((block_rows, n2), dtype=torch.float32, device=e1.device)
+    indptr = torch.zeros(n1 + 1, dtype=torch.int64, device=e1.device)
+    check(lib().oea_sim_csr_count(_p(e1), n1, e1.shape[1], _p(e2), n2, e2.shape[1], dim, float(threshold), block_rows, _p(buf),
+                                  _p(indptr), _stream()))
+    nnz = int(indptr[n1].item())
+    col = torch.zeros(max(nnz, 1), dtype=torch.int32, device=e1.device)
+    val = torch.zeros(max(nnz, 1), dtype=torch.float32, device=e1.device)
+    mismatch = torch.zeros(1, dtype=torch.int32, device=e1.device)
+    check(lib().oea_sim_csr_fill(_p(e1), n1, e1.shape[1], _p(e2), n2, e2.shape[1], dim, float(threshold), block_rows, _p(buf),
+                                 _p(indptr), _p(col), _p(val), _p(mismatch), _stream()))
+    if int(mismatch.item()) != 0:
+        raise OpenEAHipError("sim_csr: %d rows kept another number of entries in the fill pass than in the count pass"
+                             % int(mismatch.item()))
+    return indptr, col[:nnz], val[:nnz]
+
+
+def jape_sim_loss(ent, dim, ref1_ids, ref2_ids, indptr, col, val, rows, beta, loss_accum):
+    """loss_accum += beta sum_i |l2n(ent)[ref1_ids[rows[i]]] - l2n(sum_j val_ij l2n(ent)[ref2_ids[col_ij]])|^2 over the CSR rows
+    `rows` (oea_jape_sim_loss); writes nothing else."""
+    assert indptr.numel() == ref1_ids.numel() + 1
+    if col.numel() == 0:              # an empty matrix: the call wants pointers all the same and reads nothing through them
+        col, val = torch.zeros(1, dtype=torch.int32, device=ent.device), torch.zeros(1, dtype=torch.float32, device=ent.device)
+    check(lib().oea_jape_sim_loss(_p(ent), ent.shape[0], dim, ent.shape[1], _p(ref1_ids), ref1_ids.numel(), _p(ref2_ids),
+                                  ref2_ids.numel(), _p(indptr), _p(col), _p(val),
+                                  _p(rows), rows.numel(), float(beta), _p(loss_accum), _stream()))
+
+
+ATTR2VEC_VARS = ("embeds", "nce_weights", "nce_biases")
+LOG_UNIFORM_STEPS_MAX_CLASSES = 8192
+
+
+def log_uniform_sample_steps(n_classes, n_sampled, seed, step0, n_steps, thresholds, out=None):
+    """The candidate sets of steps step0 .. step0 + n_steps in one launch (oea_log_uniform_sample_steps) -> (ids int32 [n_steps, S],
+    num_tries int64 [n_steps], log Q fp32 [n_steps, S], status int32 [n_steps]): per step what LogUniformSampler.sample writes,
+    without its host wait; status != 0 marks a step whose draw did not finish (check it once per epoch)."""
+    dev = thresholds.device
+    if out is None:
+        out = (torch.zeros((n_steps, n_sampled), dtype=torch.int32, device=dev), torch.zeros(n_steps, dtype=torch.int64, device=dev),
+               torch.zeros((n_steps, n_sampled), dtype=torch.float32, device=dev), torch.zeros(n_steps, dtype=torch.int32, device=dev))
+    ids, tries, logq, status = out
+    check(lib().oea_log_uniform_sample_steps(int(n_classes), int(n_sampled), int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1),
+                                             int(n_steps), _p(thresholds), _p(ids), _p(tries), _p(logq), _p(status), _stream()))
+    return out
+
+
+def attr2vec_workspace(n_attr, ld, max_sampled, dev=None):
+    """workspace of attr2vec_step / attr2vec_epoch for up to max_sampled candidates (zeroed once)"""
+    n = lib().oea_attr2vec_workspace_bytes(int(n_attr), int(ld), int(max_sampled))
+    if n == 0:
+        raise OpenEAHipError("oea_attr2vec_workspace_bytes: n_attr=%d ld=%d max_sampled=%d" % (n_attr, ld, max_sampled))
+    ws = torch.zeros(n, dtype=torch.uint8, device=dev or device())
+    ws._shape = (int(n_attr), int(ld), int(max_sampled))
+    return ws
+
+
+def attr2vec_grads(workspace):
+    """views of the three dense fp32 gradients a PHASE_GRAD call left in the workspace, in the order of ATTR2VEC_VARS"""
+    n_attr, ld, max_s = workspace._shape
+    ptrs = (C.c_void_p * 3)()
+    check(lib().oea_attr2vec_grads(_p(workspace), n_attr, ld, max_s, ptrs))
+    out = []
+    for ptr, shape in zip(ptrs, ((n_attr, ld), (n_attr, ld), (n_attr,))):
+        off = ptr - workspace.data_ptr()
+        out.append(workspace[off:off + 4 * int(np.prod(shape))].view(torch.float32).view(shape))
+    return out
+
+
+def _attr2vec_vars(variables, accs):
+    accs = accs or (None, None, None)
+    for t in list(variables) + [a for a in accs if a is not None]:
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
+    v = _lib.Attr2VecVars(*[None if t is None else t.data_ptr() for pair in zip(variables, accs) for t in pair])
+    v._keep = (variables, accs)
+    return v
+
+
+def attr2vec_step(variables, accs, dim, pairs, sampled, log_q, num_tries, lr, workspace, loss_accum, phase=PHASE_BOTH):
+    """One Attr2Vec step in place (oea_attr2vec_step).  variables = (embeds [A, ld], nce_weights [A, ld], nce_biases [A]), accs their
+    Adagrad accumulators; pairs int32 [B, 2] = (input, label); sampled / log_q [S] and num_tries (int64 [1]) from a sampler.  The
+    batch mean is added to `loss_accum`."""
+    n_attr, ld, max_s = workspace._shape
+    assert variables[0].shape == (n_attr, ld) and pairs.dtype == torch.int32 and pairs.shape[1] == 2
+    check(lib().oea_attr2vec_step(C.byref(_attr2vec_vars(variables, accs)), n_attr, dim, ld, _p(pairs), pairs.shape[0], _p(sampled),
+                                  sampled.numel(), _p(log_q), _p(num_tries), float(lr), _p(workspace), max_s, _p(loss_accum),
+                                  int(phase), _stream()))
+
+
+def attr2vec_epoch(variables, accs, dim, pairs, batch, steps, seed, step0, thresholds, n_sampled, lr, workspace, loss_accum,
+                   buffers=None):
+    """`steps` Attr2Vec steps over the device list pairs [n_pairs, 2] in one call (oea_attr2vec_epoch): step s trains on
+    pairs[sample_distinct(n_pairs, batch, seed, step0 + s)] with the candidates of log_uniform_sample_steps(seed, step0 + s).
+    -> buffers (ids, num_tries, log_q, status, batch_idx) to pass back in; status is NOT read here."""
+    n_attr, ld, max_s = workspace._shape
+    dev = pairs.device
+    if buffers is None:
+        buffers = (torch.zeros((steps, n_sampled), dtype=torch.int32, device=dev), torch.zeros(steps, dtype=torch.int64, device=dev),
+                   torch.zeros((steps, n_sampled), dtype=torch.float32, device=dev), torch.zeros(steps, dtype=torch.int32, device=dev),
+                   torch.zeros(batch, dtype=torch.int32, device=dev))
+    ids, tries, logq, status, idx = buffers
+    assert ids.shape == (steps, n_sampled) and idx.numel() >= batch
+    check(lib().oea_attr2vec_epoch(C.byref(_attr2vec_vars(variables, accs)), n_attr, dim, ld, _p(pairs), pairs.shape[0], int(batch),
+                                   int(steps), int(seed) & (2 ** 64 - 1), int(step0) & (2 ** 64 - 1), _p(thresholds), int(n_sampled),
+                                   _p(ids), _p(tries), _p(logq), _p(status), _p(idx), float(lr), _p(workspace), max_s, _p(loss_accum),
+                                   _stream()))
+    return buffers
+
+
 # ---- ProjE ------------------------------------------------------------------------------------------------------
 PROJE_MAX_DIM = 128
 PROJE_VARS = ("ent_embeds", "rel_embeds", "entity_w", "entity_b", "input_bn_beta", "mlp_w", "mlp_bias", "output_bn_beta")
