@@ -362,6 +362,45 @@ int oea_sim_csr_fill(const float *e1, int64_t n1, int32_t ld1, const float *e2, 
 int oea_jape_sim_loss(const float *ent, int64_t n_ent, int32_t dim, int32_t ld, const int32_t *ref1_ids, int64_t n_ref1,
                       const int32_t *ref2_ids, int64_t n_ref2, const int64_t *indptr, const int32_t *col, const float *val,
                       const int32_t *rows, int64_t m, float beta, double *loss_accum, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * IMUSE's string similarity (approaches/imuse.py:42-66, 195-249; csrc/lcs_sim.hip).  Levenshtein.ratio(a, b) =
+ * 2 LCS(a, b) / (|a| + |b|) over code points, 1.0 when both are empty; LCS by the bit-vector recurrence with the pattern's
+ * character masks in an LDS table (patterns up to 256 code points), by a wave-wide row DP beyond that.  Integers are exact and the
+ * ratio is (double)(2 lcs) / (double)(|a| + |b|): the bits Python gives.
+ *
+ * STRING POOL (one per KG side, built once on the host): cp int32 [n_cp] = the distinct strings as UTF-32 code points back to back
+ * (each in [0, 0x10FFFF]), off int64 [n_str + 1] with off[0] = 0 and off[n_str] = n_cp.  max_len: the caller's bound on the length
+ * of any string of either pool.  workspace: oea_lcs_workspace_ints(max_len) int32 of device memory.
+ *
+ * What the host sees is refused by the return status before any launch: a null pointer, n_str < 1, n_cp < 0, max_len < 0, n < 0,
+ * K < 1 or K > 32, n1 < 1, n2 < 1, cap < 1, a NaN threshold -> OEA_EINVAL.  What lies in device memory -- offsets that decrease,
+ * do not start at 0 or end at n_cp, a string longer than max_len, an index outside its pool, a row outside [0, n1) -- is found by
+ * check kernels that run first on the stream: they set *err_flag (device int32, zeroed by the caller; bit 0 a pool, bit 1 an index)
+ * and the compute kernels then write NOTHING.  The caller reads err_flag with the results.  No host synchronisation inside.
+ * ------------------------------------------------------------------------------------- */
+size_t oea_lcs_workspace_ints(int64_t max_len);
+/* pairs int32 [n, 2] = (string of pool 1, string of pool 2) -> lcs int32 [n], ratio fp64 [n].  One wave per pair; the shorter
+ * string is the pattern, so only a pair whose SHORTER side exceeds 256 code points takes the row DP. */
+int oea_lcs_ratio_pairs(const int32_t *cp1, const int64_t *off1, int64_t n_str1, int64_t n_cp1, const int32_t *cp2, const int64_t *off2,
+                        int64_t n_str2, int64_t n_cp2, int64_t max_len, const int32_t *pairs, int64_t n, int32_t *lcs, double *ratio,
+                        int32_t *workspace, int32_t *err_flag, void *stream);
+/* The records of run_one_ea's walk (imuse.py:47-62), without the n1 x n2 matrix.  K aligned attribute pairs IN THE CALLER'S ORDER;
+ * idx1 int32 [K, n1] / idx2 int32 [K, n2]: the value (an index into pool 1 / pool 2) that entity i / j holds for pair k, -1 for
+ * none.  For row i and j = 0 .. n2 - 1 in order, in fp64:
+ *     s = 0, c = 0;  for k = 0 .. K - 1: if both present: s += ratio(value1, value2), c += 1;   if c > 0: s /= c
+ * and (j, s) is a RECORD when s > threshold and s > every earlier s of the row (strictly: a tie is none).
+ * rows int32 [n_rows] (NULL: all n1 rows, n_rows == n1) selects the rows; output slot r belongs to rows[r]:
+ *     rec_col int32 [n_rows, cap], rec_val fp64 [n_rows, cap]   the first min(count, cap) records of the row, j ascending
+ *     rec_cnt int32 [n_rows] = min(count, cap),  overflow int32 [n_rows] = 1 when the row has more than cap records
+ * A caller must rerun the rows that overflowed with a larger cap: no record is dropped without the flag.
+ * One workgroup per row: the row's K tables are built once and serve the whole walk. */
+int oea_attr_sim_records(const int32_t *cp1, const int64_t *off1, int64_t n_str1, int64_t n_cp1, const int32_t *cp2, const int64_t *off2,
+                         int64_t n_str2, int64_t n_cp2, int64_t max_len, int32_t K, const int32_t *idx1, int64_t n1,
+                         const int32_t *idx2, int64_t n2, double threshold, const int32_t *rows, int64_t n_rows, int32_t cap,
+                         int32_t *rec_col, double *rec_val, int32_t *rec_cnt, int32_t *overflow, int32_t *workspace, int32_t *err_flag,
+                         void *stream);
+
 /* The candidate sets of n_steps steps in ONE launch, for the steps that are too short to wait for oea_log_uniform_sample's status
  * word (declared with ProjE below; the values here are its values bit for bit): workgroup s writes out_ids[s, :], out_num_tries[s],
  * out_log_q_sampled[s, :] of step step0 + s, and status[s] = 0, or 1 when n_sampled distinct classes did not appear in 64 n_sampled

@@ -199,6 +199,10 @@ PROTOTYPES = {
     "oea_sim_csr_count": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _f32, _i64, _vp, _vp, _vp]),
     "oea_sim_csr_fill": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "oea_jape_sim_loss": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp]),
+    "oea_lcs_workspace_ints": (_sz, [_i64]),
+    "oea_lcs_ratio_pairs": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "oea_attr_sim_records": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _i64, C.c_double, _vp, _i64,
+                                       _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "oea_log_uniform_sample_steps": (C.c_int, [_i64, _i64, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "oea_attr2vec_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "oea_attr2vec_grads": (C.c_int, [_vp, _i64, _i32, _i64, C.POINTER(C.c_void_p)]),

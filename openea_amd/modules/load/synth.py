@@ -6,6 +6,7 @@ degrees; every entity occurs in at least one triple; entity i of KG1 is aligned 
 of KG2; links are split 20% / 10% / 70% (README.md:252-255).
 """
 import os
+import random
 
 import numpy as np
 
@@ -71,10 +72,47 @@ def generate_uri_dataset(shape="EN-FR-15K-V1", seed=0):
     return tri1, tri2, links[:n_train], links[n_train:n_train + n_valid], links[n_train + n_valid:]
 
 
-def _attribute_triples(rng, prefix, profile, n_att, n_tri):
+# the alphabet of the synthetic string values: mostly ASCII, a share of accented Latin, Greek and CJK, a few above U+FFFF
+_VALUE_ALPHABET = ("abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789 -.,'" * 2
+                   + "\u00e9\u00e8\u00e0\u00fc\u00f6\u00e4\u00f1\u00e7\u00df\u00f8\u03b1\u03b2\u03b3\u03b4\u4e2d\u6587\u5b57\u6f22"
+                   + "\U0001f600\U00010348\U0001d11e\U00020000")
+
+
+def _string_value(seed, side, profile, ent, att):
+    """The value of (entity ent, attribute att) on KG side `side` as a string of 3 to 40 code points (a few empty, a few above 64
+    and above 256): a base string that depends on (profile, ent, att) only, so that the aligned entities of the two KGs share it
+    under the attribute of the same number, with 0 to 5 random edits that depend on the side as well."""
+    # random.Random seeded with an int (init_by_array of the Mersenne twister) and read through random() alone: the same
+    # strings on every Python 3; a numpy RandomState per value costs a millisecond, this a few microseconds
+    key = (((int(seed) & 0x7fffffff) * 64 + int(profile)) * (1 << 24) + int(ent)) * (1 << 12) + int(att)
+    base = random.Random(key * 4 + 1)
+    kind = int(base.random() * 400)
+    if kind < 6:
+        return ""
+    n = 3 + int(base.random() * 38)
+    if kind < 10:
+        n = 65 + int(base.random() * 65)
+    elif kind < 12:
+        n = 257 + int(base.random() * 143)
+    chars = [_VALUE_ALPHABET[int(base.random() * len(_VALUE_ALPHABET))] for _ in range(n)]
+    edit = random.Random(key * 4 + 1 + int(side))
+    for _ in range(int(edit.random() * 6)):
+        at, what = int(edit.random() * (len(chars) + 1)), int(edit.random() * 3)
+        c = _VALUE_ALPHABET[int(edit.random() * len(_VALUE_ALPHABET))]
+        if what == 0 or not chars:
+            chars.insert(at, c)
+        elif what == 1:
+            chars[min(at, len(chars) - 1)] = c
+        else:
+            del chars[min(at, len(chars) - 1)]
+    return "".join(chars)
+
+
+def _attribute_triples(rng, prefix, profile, n_att, n_tri, string_values=None):
     """n_tri (entity, attribute, value) triples over n_att attributes: entity i holds n_tri / n_ent distinct attributes (rounded so
     that the total is exact) drawn without replacement under the weights of its latent profile -- a Zipf law over a
-    profile-specific order of the KG's attributes, so that two entities of one profile share most of theirs"""
+    profile-specific order of the KG's attributes, so that two entities of one profile share most of theirs.
+    string_values = (seed, side): the values are _string_value's strings instead of "v<number>"."""
     n_ent = len(profile)
     counts = np.full(n_ent, n_tri // n_ent, np.int64)
     counts[rng.permutation(n_ent)[:n_tri - counts.sum()]] += 1
@@ -88,26 +126,30 @@ def _attribute_triples(rng, prefix, profile, n_att, n_tri):
         pick = np.argsort(-score, axis=1)
         for i in range(lo, hi):
             for a in pick[i - lo, :counts[i]]:
-                out.add(("%s/e%d" % (prefix, i), "%s/a%d" % (prefix, a), "v%d" % ((i * 31 + int(a)) % 97)))
+                value = "v%d" % ((i * 31 + int(a)) % 97) if string_values is None else _string_value(*string_values, profile[i], i, a)
+                out.add(("%s/e%d" % (prefix, i), "%s/a%d" % (prefix, a), value))
     return out
 
 
-def generate_attribute_triples(shape="EN-FR-15K-V1", seed=0):
+def generate_attribute_triples(shape="EN-FR-15K-V1", seed=0, string_values=False):
     """-> (attribute triples of KG1, of KG2) as URI triples.  Entity i of KG1 and entity i of KG2 (aligned) share one latent profile;
     each KG maps a profile to its own attributes, so attribute co-occurrence across the training links carries the signal JAPE's
-    Attr2Vec reads.  A stream of its own: the relation triples and links of generate_uri_dataset do not change."""
+    Attr2Vec reads.  A stream of its own: the relation triples and links of generate_uri_dataset do not change.
+    string_values: the values are strings that IMUSE's similarity can read (_string_value; streams of their own again, so the
+    entities' attributes are the same either way); off, the values are "v<number>" as before."""
     n_ent = SHAPES[shape][0]
     (a1, a2), (t1, t2) = ATTRIBUTES[shape]
     rng = np.random.RandomState([seed, 0xa77])
     profile = rng.randint(0, N_PROFILES, n_ent)
-    return _attribute_triples(rng, "kg1", profile, a1, t1), _attribute_triples(rng, "kg2", profile, a2, t2)
+    return (_attribute_triples(rng, "kg1", profile, a1, t1, (seed, 1) if string_values else None),
+            _attribute_triples(rng, "kg2", profile, a2, t2, (seed, 2) if string_values else None))
 
 
-def make_kgs(shape="EN-FR-15K-V1", mode="mapping", ordered=True, seed=0, verbose=False, attributes=False):
+def make_kgs(shape="EN-FR-15K-V1", mode="mapping", ordered=True, seed=0, verbose=False, attributes=False, string_values=False):
     """-> KGs built through the same id-assignment code as a real dataset.  attributes=True adds generate_attribute_triples (for
-    the shapes in ATTRIBUTES); the default has none, as before."""
+    the shapes in ATTRIBUTES); the default has none, as before.  string_values=True (with attributes): string values."""
     tri1, tri2, train, valid, test = generate_uri_dataset(shape, seed)
-    att1, att2 = generate_attribute_triples(shape, seed) if attributes else (set(), set())
+    att1, att2 = generate_attribute_triples(shape, seed, string_values) if attributes else (set(), set())
     return KGs(KG(tri1, att1, verbose=verbose), KG(tri2, att2, verbose=verbose), train, test, valid_links=valid,
                mode=mode, ordered=ordered, verbose=verbose)
 

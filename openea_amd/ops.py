@@ -363,6 +363,110 @@ def jape_sim_loss(ent, dim, ref1_ids, ref2_ids, indptr, col, val, rows, beta, lo
                                   _p(rows), rows.numel(), float(beta), _p(loss_accum), _stream()))
 
 
+# ---- IMUSE: string similarity (csrc/lcs_sim.hip) ----------------------------------------------------------------------
+class StringPool:
+    """The distinct strings of one KG side for oea_lcs_ratio_pairs / oea_attr_sim_records: int32 code points back to back (UTF-32:
+    the reference compares the elements of a str) + int64 offsets, on the device.  Strings are taken as they come: no strip, no
+    lower-casing.  `ids(strings)` -> their indices (int32)."""
+
+    def __init__(self, strings, dev=None):
+        self.index = {}
+        for s in strings:
+            if s not in self.index:
+                self.index[s] = len(self.index)
+        parts = [np.frombuffer(s.encode('utf-32-le', 'surrogatepass'), dtype='<u4').astype(np.int32) for s in self.index]
+        self.lengths = np.array([len(p) for p in parts], np.int64)
+        self.n_str, self.n_cp = len(parts), int(self.lengths.sum())
+        self.max_len = int(self.lengths.max()) if parts else 0
+        off = np.zeros(self.n_str + 1, np.int64)
+        np.cumsum(self.lengths, out=off[1:])
+        cp = np.concatenate(parts) if self.n_cp else np.zeros(1, np.int32)            # never a null pointer
+        dev = dev or device()
+        self.cp, self.off = torch.from_numpy(cp).to(dev), torch.from_numpy(off).to(dev)
+
+    def ids(self, strings):
+        return np.array([self.index[s] for s in strings], np.int32)
+
+    def _args(self):
+        return _p(self.cp), _p(self.off), self.n_str, self.n_cp
+
+
+def _lcs_workspace(pool1, pool2):
+    max_len = max(pool1.max_len, pool2.max_len)
+    return max_len, torch.empty(max(lib().oea_lcs_workspace_ints(max_len), 1), dtype=torch.int32, device=pool1.cp.device)
+
+
+def lcs_check(err_flag):
+    """what the check kernels of the two calls below found in device memory (reads the flag: a host wait)"""
+    e = int(err_flag.item())
+    if e:
+        raise OpenEAHipError("string similarity refused its device arguments (nothing was written):%s%s"
+                             % (" a pool's offsets do not start at 0, decrease, end elsewhere than at n_cp or pass max_len;" if e & 1 else "",
+                                " an index lies outside its pool or a row outside [0, n1)" if e & 2 else ""))
+
+
+def lcs_ratio_pairs(pool1, pool2, pairs, out=None, err_flag=None):
+    """pairs device int32 [n, 2] (string of pool1, string of pool2) -> (lcs int32 [n], ratio fp64 [n]) = (LCS length,
+    Levenshtein.ratio = 2 lcs / (len1 + len2), 1.0 for two empty strings) (oea_lcs_ratio_pairs).  With err_flag given (device
+    int32 [1], zeroed) the caller checks it (lcs_check); otherwise this call does, which waits for the device."""
+    n = pairs.shape[0]
+    dev = pool1.cp.device
+    lcs, ratio = out if out is not None else (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
+    flag = err_flag if err_flag is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+    max_len, ws = _lcs_workspace(pool1, pool2)
+    check(lib().oea_lcs_ratio_pairs(*pool1._args(), *pool2._args(), max_len, _p(pairs), n, _p(lcs), _p(ratio), _p(ws), _p(flag), _stream()))
+    if err_flag is None:
+        lcs_check(flag)
+    return lcs, ratio
+
+
+def attr_sim_records_raw(pool1, pool2, idx1, idx2, threshold, cap, rows=None, out=None, err_flag=None):
+    """One oea_attr_sim_records call, nothing read back -> (rec_col int32 [n_rows, cap], rec_val fp64 [n_rows, cap], rec_cnt int32
+    [n_rows], overflow int32 [n_rows], err_flag)."""
+    K, n1 = idx1.shape
+    n2 = idx2.shape[1]
+    dev = idx1.device
+    n_rows = n1 if rows is None else rows.numel()
+    if out is None:
+        out = (torch.empty((n_rows, max(cap, 0)), dtype=torch.int32, device=dev), torch.empty((n_rows, max(cap, 0)), dtype=torch.float64, device=dev),
+               torch.empty(n_rows, dtype=torch.int32, device=dev), torch.empty(n_rows, dtype=torch.int32, device=dev))
+    flag = err_flag if err_flag is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+    max_len, ws = _lcs_workspace(pool1, pool2)
+    check(lib().oea_attr_sim_records(*pool1._args(), *pool2._args(), max_len, K, _p(idx1), n1, _p(idx2), n2, float(threshold), _p(rows),
+                                     n_rows, int(cap), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _p(ws), _p(flag), _stream()))
+    return out + (flag,)
+
+
+def attr_sim_records(pool1, pool2, idx1, idx2, threshold, cap=16):
+    """The records of every row of run_one_ea's walk (imuse.py:47-62) as a host CSR -> (ptr int64 [n1 + 1], col int32 [nnz], val fp64
+    [nnz]): row i's records are the (j, s), j ascending, with s > threshold and s > every earlier s of the row, s the mean
+    Levenshtein.ratio over the aligned attribute pairs both entities hold.  idx1 int32 [K, n1] / idx2 int32 [K, n2] on the device:
+    value indices into the pools, -1 for none.  Rows that have more than `cap` records are run again with twice the capacity
+    until none is left: no record is lost."""
+    n1 = idx1.shape[1]
+    counts = np.zeros(n1, np.int64)
+    passes = []
+    rows, rows_h = None, np.arange(n1)
+    while rows_h.size:
+        rec_col, rec_val, rec_cnt, overflow, flag = attr_sim_records_raw(pool1, pool2, idx1, idx2, threshold, cap, rows)
+        lcs_check(flag)
+        done = overflow.cpu().numpy() == 0
+        cnt = rec_cnt.cpu().numpy().astype(np.int64)[done]
+        counts[rows_h[done]] = cnt
+        passes.append((rows_h[done], cnt, rec_col.cpu().numpy()[done], rec_val.cpu().numpy()[done]))
+        rows_h = rows_h[~done]
+        rows = to_ids(rows_h, idx1.device)
+        cap *= 2
+    ptr = np.zeros(n1 + 1, np.int64)
+    np.cumsum(counts, out=ptr[1:])
+    col, val = np.empty(ptr[-1], np.int32), np.empty(ptr[-1], np.float64)
+    for r, cnt, c, v in passes:
+        keep = np.arange(c.shape[1])[None, :] < cnt[:, None]
+        at = (ptr[r][:, None] + np.arange(c.shape[1])[None, :])[keep]
+        col[at], val[at] = c[keep], v[keep]
+    return ptr, col, val
+
+
 ATTR2VEC_VARS = ("embeds", "nce_weights", "nce_biases")
 LOG_UNIFORM_STEPS_MAX_CLASSES = 8192
 
