@@ -19,97 +19,19 @@
 // Rows that repeat (an input in many pairs, a repeated label, a label that is also a candidate) are summed in the step scratch's
 // element type: fp32 atomics, or int64 fixed point in the deterministic build, where every other sum above has a fixed order.
 //
-// oea_log_uniform_sample_steps: the candidate sets of many steps in one launch, one workgroup per step with the first-appearance
-// table in LDS; the values are those of oea_log_uniform_sample (proje_step.hip) bit for bit, and a status word per step stands
-// in for that call's host wait.
-#include "nce_half.h"
+// The candidates come from log_uniform.hip; oea_attr2vec_epoch takes those of all its steps from oea_log_uniform_sample_steps, whose
+// status word per step the kernels here read.
+#include "row_ops.h"
+
+#include <algorithm>
 
 namespace {
 
-constexpr int kStepsThreads = 1024;
-constexpr int kStepsPer = 4;
-constexpr int kStepsChunk = kStepsThreads * kStepsPer;
-constexpr int kStepsMaxClasses = OEA_LOG_UNIFORM_STEPS_MAX_CLASSES;     // first[] in LDS: 32 KB
+using oea::grad_t;
+using namespace oea::row;
 
-// sample_kernel of proje_step.hip with first[] in LDS and no list of drawn classes (nothing to clear on the way out)
-__global__ __launch_bounds__(kStepsThreads) void sample_steps_kernel(int n_classes, int n_sampled, uint64_t seed, uint64_t step0,
-                                                                     const double *__restrict__ thr, int32_t *out_ids_all,
-                                                                     int64_t *out_tries_all, float *out_logq_all, int32_t *status_all,
-                                                                     int64_t max_tries) {
-    __shared__ uint32_t first[kStepsMaxClasses];
-    __shared__ int wave_tot[kStepsThreads / 64];
-    __shared__ int s_found;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t step = step0 + blockIdx.x;
-    int32_t *out_ids = out_ids_all + (int64_t)blockIdx.x * n_sampled;
-    float *out_logq = out_logq_all + (int64_t)blockIdx.x * n_sampled;
-    for (int c = tid; c < n_classes; c += kStepsThreads) first[c] = 0u;
-    if (tid == 0) s_found = -1;
-    int have = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < max_tries; base += kStepsChunk) {
-        const int64_t t0 = base + (int64_t)tid * kStepsPer;
-        const uint4 w4 = oea::philox4x32_10((uint32_t)(t0 >> 2), 0x50726a45u, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-                                            (uint32_t)(seed >> 32));
-        const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-        int32_t c[kStepsPer];
-#pragma unroll
-        for (int i = 0; i < kStepsPer; ++i) {
-            const double u = ((double)w[i] + 0.5) * 2.3283064365386963e-10;
-            int lo = 0, hi = n_classes - 1;              // first c with u < T[c]; T[n - 1] = 1 > u
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (u < thr[mid]) hi = mid; else lo = mid + 1;
-            }
-            c[i] = lo;
-            if (t0 + i < max_tries) atomicMax(first + lo, ~(uint32_t)(t0 + i));
-        }
-        __syncthreads();
-        int flag[kStepsPer], mine = 0;
-#pragma unroll
-        for (int i = 0; i < kStepsPer; ++i) {
-            flag[i] = t0 + i < max_tries && first[c[i]] == ~(uint32_t)(t0 + i);
-            mine += flag[i];
-        }
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        int before = have, total = have;
-        for (int wv = 0; wv < kStepsThreads / 64; ++wv) {
-            if (wv < wave) before += wave_tot[wv];
-            total += wave_tot[wv];
-        }
-        int rank = before + incl - mine;
-#pragma unroll
-        for (int i = 0; i < kStepsPer; ++i) {
-            if (flag[i]) {
-                if (rank < n_sampled) out_ids[rank] = c[i];
-                if (rank == n_sampled - 1) s_found = (int)(t0 + i);
-                ++rank;
-            }
-        }
-        have = total;
-        __syncthreads();
-        if (have >= n_sampled) break;
-    }
-    const int found = s_found;
-    if (found < 0) {        // not reached in 64 S tries: valid ids all the same (a caller that ignores the status stays in bounds)
-        for (int j = tid; j < n_sampled; j += kStepsThreads) { out_ids[j] = j; out_logq[j] = 0.f; }
-        if (tid == 0) { status_all[blockIdx.x] = 1; out_tries_all[blockIdx.x] = 1; }
-        return;
-    }
-    const double n_tries = (double)(found + 1), inv = 1.0 / log((double)n_classes + 1.0);
-    if (tid == 0) { status_all[blockIdx.x] = 0; out_tries_all[blockIdx.x] = found + 1; }
-    __threadfence();
-    __syncthreads();
-    for (int j = tid; j < n_sampled; j += kStepsThreads)
-        out_logq[j] = (float)log_q(__hip_atomic_load(out_ids + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), n_tries, inv);
-}
+constexpr int kMaxDim = 128;
+constexpr int LP = 128;            // row stride of xn / wn (zero padded)
 
 // ---- workspace -------------------------------------------------------------------------------------------------------------
 struct A2V {
@@ -125,7 +47,7 @@ static A2V make_a2v(void *base, int64_t n_attr, int ld, int64_t max_s) {
     A2V L;
     size_t o = 0;
     char *b = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { char *at = b + o; o += al(bytes); return at; };
+    auto take = [&](size_t bytes) { char *at = b + o; o += oea::align256(bytes); return at; };
     const size_t A = (size_t)n_attr, Sp = ((size_t)max_s + 63) / 64 * 64;
     L.sp = (int64_t)Sp;
     L.g_emb = (float *)take(4 * A * ld); L.g_w = (float *)take(4 * A * ld); L.g_b = (float *)take(4 * A);
@@ -159,19 +81,7 @@ __device__ __forceinline__ void add_row(grad_t *p, float2 g, int dim, int lane) 
     if (c + 1 < dim) oea::grad_add(p + c + 1, g.y);
 }
 
-__device__ __forceinline__ void block_loss(double v, double *loss_accum, double *wave_loss) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_loss[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < 4; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(loss_accum, s);
-    }
-}
-
 __global__ __launch_bounds__(256) void true_kernel(StepArgs A) {
-    __shared__ double wave_loss[4];
     if (A.status && *A.status != 0) return;        // grid-uniform
     const int lane = threadIdx.x & 63;
     const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
@@ -195,7 +105,7 @@ __global__ __launch_bounds__(256) void true_kernel(StepArgs A) {
             A.W.tx[in] = 1; A.W.tw[lab] = 1;
         }
     }
-    block_loss(loss_local, A.loss_accum, wave_loss);
+    oea::block_loss_add<4>(loss_local, lane, threadIdx.x >> 6, A.loss_accum);
 }
 
 __global__ __launch_bounds__(256) void cand_kernel(StepArgs A) {
@@ -216,7 +126,6 @@ __global__ __launch_bounds__(256) void cand_kernel(StepArgs A) {
 __global__ __launch_bounds__(256) void samp_kernel(StepArgs A) {
     __shared__ __attribute__((aligned(16))) float xs[4][LP];
     __shared__ float gs[4][64];
-    __shared__ double wave_loss[4];
     if (A.status && *A.status != 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gw = (int64_t)blockIdx.x * 4 + wave, nw = (int64_t)gridDim.x * 4;
@@ -261,7 +170,7 @@ __global__ __launch_bounds__(256) void samp_kernel(StepArgs A) {
         add_row(A.W.s_x + a * A.ld, gx, A.dim, lane);
         loss_local += (double)oea::group_sum<64>(lsum);
     }
-    block_loss(loss_local, A.loss_accum, wave_loss);
+    oea::block_loss_add<4>(loss_local, lane, wave, A.loss_accum);
 }
 
 __global__ __launch_bounds__(256) void gradw_kernel(StepArgs A) {
@@ -401,23 +310,6 @@ int launch_step(const oea_attr2vec_vars *v, const A2V &W, int64_t n_attr, int di
 
 extern "C" {
 
-int oea_log_uniform_sample_steps(int64_t n_classes, int64_t n_sampled, uint64_t seed, uint64_t step0, int64_t n_steps,
-                                 const double *thresholds, int32_t *out_ids, int64_t *out_num_tries, float *out_log_q_sampled,
-                                 int32_t *status, void *stream) {
-    OEA_REQUIRE(thresholds && out_ids && out_num_tries && out_log_q_sampled && status, "null pointer");
-    OEA_REQUIRE(n_sampled >= 1 && n_sampled <= n_classes && n_steps >= 0 && n_steps < ((int64_t)1 << 31), "1 <= n_sampled <= n_classes, n_steps");
-    if (n_classes > kStepsMaxClasses) {
-        oea::set_error("oea_log_uniform_sample_steps: n_classes %lld > %d (the first-appearance table lives in LDS; "
-                       "oea_log_uniform_sample has no limit)", (long long)n_classes, kStepsMaxClasses);
-        return OEA_EUNSUPPORTED;
-    }
-    if (n_steps == 0) return OEA_OK;
-    sample_steps_kernel<<<(unsigned)n_steps, kStepsThreads, 0, oea::as_stream(stream)>>>(
-        (int)n_classes, (int)n_sampled, seed, step0, thresholds, out_ids, out_num_tries, out_log_q_sampled, status, 64 * n_sampled);
-    OEA_CHECK_HIP(hipGetLastError());
-    return OEA_OK;
-}
-
 size_t oea_attr2vec_workspace_bytes(int64_t n_attr, int32_t ld, int64_t max_sampled) {
     if (n_attr < 1 || ld < 4 || ld % 4 != 0 || max_sampled < 1 || max_sampled >= ((int64_t)1 << 24)) return 0;
     return make_a2v(nullptr, n_attr, ld, max_sampled).total;
@@ -452,8 +344,9 @@ int oea_attr2vec_epoch(const oea_attr2vec_vars *vars, int64_t n_attr, int32_t di
     OEA_REQUIRE(workspace && loss_accum && pairs && thresholds && cand_ids && cand_tries && cand_log_q && cand_status && batch_idx,
                 "null pointer");
     OEA_REQUIRE(n_pairs >= n_batch && n_pairs < ((int64_t)1 << 31), "batch <= n_pairs < 2^31");
-    if (n_attr > kStepsMaxClasses) {
-        oea::set_error("oea_attr2vec_epoch: n_attr %lld > %d (oea_log_uniform_sample_steps)", (long long)n_attr, kStepsMaxClasses);
+    if (n_attr > OEA_LOG_UNIFORM_STEPS_MAX_CLASSES) {
+        oea::set_error("oea_attr2vec_epoch: n_attr %lld > %d (oea_log_uniform_sample_steps)", (long long)n_attr,
+                       OEA_LOG_UNIFORM_STEPS_MAX_CLASSES);
         return OEA_EUNSUPPORTED;
     }
     int rs = oea_log_uniform_sample_steps(n_attr, n_sampled, seed, step0, steps, thresholds, cand_ids, cand_tries, cand_log_q,

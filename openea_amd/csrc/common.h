@@ -72,6 +72,8 @@ static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }      // every workspace region starts on 256 bytes
+
 // kernel launch that carries the profile session's events when this call is a sampled one
 template <class K, class... A>
 static inline void launch_timed(K kernel, dim3 grid, dim3 block, hipStream_t st, A... args) {
@@ -138,6 +140,21 @@ __device__ __forceinline__ double group_sum_d(double v) {
 }
 __device__ __forceinline__ double wave_sum_d(double v) { return group_sum_d<64>(v); }
 
+// Block tail of a loss: lane 0 of each of the block's WAVES waves brings its wave's sum; thread 0 adds them in wave order and, unless
+// the total is zero, adds scale * total to *loss_accum.  One barrier: every thread of the block has to get here.  lane and wave are
+// the caller's own (threadIdx.x & 63, threadIdx.x >> 6), as for the row helpers.
+template <int WAVES>
+__device__ __forceinline__ void block_loss_add(double v, int lane, int wave, double *loss_accum, double scale = 1.0) {
+    __shared__ double wave_loss[WAVES];
+    if (lane == 0) wave_loss[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < WAVES; ++w) s += wave_loss[w];
+        if (s != 0.0) atomicAdd(loss_accum, scale * s);
+    }
+}
+
 // hardware fp32 atomic add (global_atomic_add_f32, no CAS loop); device scope.
 __device__ __forceinline__ void atomic_add_f32(float *p, float v) { unsafeAtomicAdd(p, v); }
 
@@ -181,6 +198,11 @@ __device__ __forceinline__ void grad_add(float *p, float v) { unsafeAtomicAdd(p,
 __device__ __forceinline__ void grad_add_raw(float *p, float q) { unsafeAtomicAdd(p, q); }
 #endif
 
+// where a step that rides on the engine adds its rows: the entity rows, copy 0 of the relation rows, and their touched flags inside
+// a step workspace (triple_step.hip, the one place that knows the order of the regions)
+void step_scratch_rows(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, grad_t **ent_grad, flag_t **ent_touched,
+                       grad_t **rel_grad, flag_t **rel_touched);
+
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 
@@ -197,6 +219,33 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
         k0 += W0; k1 += W1;
     }
     return make_uint4(c0, c1, c2, c3);
+}
+
+// ---- keyed permutation of [0, n): 4-round Feistel network on the index bits + cycle walking (oea_perm_index; bit-identical with
+// oracle/np_oracle.py).  sample_distinct.hip and step_plan.hip have 6-round networks of their own: other bijections.
+__host__ __device__ __forceinline__ uint32_t feistel_f(uint32_t r, uint32_t key, uint32_t round) {
+    uint32_t v = r * 0x9E3779B1u + key + round * 0x85EBCA6Bu;
+    v ^= v >> 15; v *= 0x2C1B3C6Du;
+    v ^= v >> 12; v *= 0x297A2D39u;
+    v ^= v >> 15;
+    return v;
+}
+__host__ __device__ __forceinline__ uint32_t perm_index(uint32_t i, uint32_t n, uint32_t key) {
+    uint32_t bits = 2;
+    while ((1u << bits) < n) bits += 2;
+    const uint32_t half = bits >> 1, mask = (1u << half) - 1u;
+    uint32_t x = i;
+    do {
+        uint32_t l = x >> half, r = x & mask;
+#pragma unroll
+        for (uint32_t round = 0; round < 4; ++round) {
+            const uint32_t t = l ^ (feistel_f(r, key, round) & mask);
+            l = r;
+            r = t;
+        }
+        x = (l << half) | r;
+    } while (x >= n);
+    return x;
 }
 
 // ---- triple membership set (layout shared with oracle/c/oracle.c) ---------------------------

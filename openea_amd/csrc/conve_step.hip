@@ -71,7 +71,7 @@ struct CLayout {
 static CLayout make_layout(int64_t n_ent, int64_t n_rel, int dim, int ld, int F, int64_t max_pos, int64_t max_s) {
     CLayout L;
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+    auto take = [&](size_t bytes) { const size_t at = o; o += oea::align256(bytes); return at; };
     const size_t E = (size_t)n_ent, R = (size_t)n_rel, B = (size_t)max_pos, S = (size_t)max_s, K = (size_t)2 * dim * F;
     L.g_ent = take(4 * E * ld); L.g_rel = take(4 * R * ld); L.g_w = take(4 * E * ld); L.g_b = take(4 * E);
     L.g_g1 = take(4 * LP); L.g_b1 = take(4 * LP); L.g_kern = take(4 * 9 * kMaxFilters); L.g_cb = take(4 * kMaxFilters);

@@ -38,7 +38,6 @@ struct JapeArgs {
 
 __global__ __launch_bounds__(64 * kWaves) void jape_kernel(JapeArgs A) {
     __shared__ __attribute__((aligned(16))) float buf[kWaves][kMaxDim];
-    __shared__ double wave_loss[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k = A.k;
     double loss_local = 0.0;
@@ -66,16 +65,8 @@ __global__ __launch_bounds__(64 * kWaves) void jape_kernel(JapeArgs A) {
         se.flush(A.ent_grad, A.ent_touched, A.ld, A.dim, lane, buf[wave]);
         sr.flush(A.rel_grad, A.rel_touched, A.ld, A.dim, lane, buf[wave]);
     }
-    if (lane == 0) wave_loss[wave] = loss_local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kWaves; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(A.loss_accum, s);
-    }
+    oea::block_loss_add<kWaves>(loss_local, lane, wave, A.loss_accum);
 }
-
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -102,28 +93,13 @@ int oea_jape_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *
         oea::set_error("oea_jape_step: dim %d > %d", dim, kMaxDim);
         return OEA_EUNSUPPORTED;
     }
-    // the step engine's scratch, laid out as oea_semantic_step finds it: [ent_grad | rel_grad | nrm_grad | ent_touched |
-    // rel_touched | nrm_touched], each region 256-byte aligned (include/openea_hip.h)
-    void *eg = nullptr, *et = nullptr;
-    int rc = oea_step_entity_scratch(step_workspace, n_ent, n_rel, ld, &eg, &et);
-    if (rc != OEA_OK) return rc;
-    int64_t ng_off = 0, nt_off = 0;
-    rc = oea_step_normal_scratch(n_ent, n_rel, ld, &ng_off, &nt_off);
-    if (rc != OEA_OK) return rc;
-    char *base = static_cast<char *>(step_workspace);
-    grad_t *rel_grad = reinterpret_cast<grad_t *>(base + ng_off - align256(sizeof(grad_t) * (size_t)n_rel * ld));
-    flag_t *rel_touched = reinterpret_cast<flag_t *>(base + nt_off - align256(sizeof(flag_t) * (size_t)n_rel));
-    OEA_REQUIRE(reinterpret_cast<char *>(rel_grad) == static_cast<char *>(eg) + align256(sizeof(grad_t) * (size_t)n_ent * ld) &&
-                    reinterpret_cast<char *>(rel_touched) == static_cast<char *>(et) + align256(sizeof(flag_t) * (size_t)n_ent),
-                "step workspace layout");
     hipStream_t st = oea::as_stream(stream);
     if (n_pos > 0) {
         JapeArgs A;
         A.ent = ent; A.rel = rel; A.ld = ld; A.dim = dim;
         A.pos = pos; A.neg = neg; A.n_pos = n_pos; A.k = (int)k;
         A.neg_alpha = neg_alpha; A.ent_l2n = cfg->ent_l2_norm; A.rel_l2n = cfg->rel_l2_norm;
-        A.ent_grad = static_cast<grad_t *>(eg); A.rel_grad = rel_grad;
-        A.ent_touched = static_cast<flag_t *>(et); A.rel_touched = rel_touched;
+        oea::step_scratch_rows(step_workspace, n_ent, n_rel, ld, &A.ent_grad, &A.ent_touched, &A.rel_grad, &A.rel_touched);
         A.loss_accum = loss_accum;
         const unsigned grid = (unsigned)std::min<int64_t>(oea::ceil_div(n_pos, kWaves), kMaxBlocks);
         jape_kernel<<<grid, 64 * kWaves, 0, st>>>(A);

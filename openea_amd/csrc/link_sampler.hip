@@ -14,31 +14,7 @@
 
 namespace {
 
-__host__ __device__ __forceinline__ uint32_t feistel_f(uint32_t r, uint32_t key, uint32_t round) {
-    uint32_t v = r * 0x9E3779B1u + key + round * 0x85EBCA6Bu;
-    v ^= v >> 15; v *= 0x2C1B3C6Du;
-    v ^= v >> 12; v *= 0x297A2D39u;
-    v ^= v >> 15;
-    return v;
-}
-// image of i under the keyed permutation of [0, n)
-__host__ __device__ __forceinline__ uint32_t perm_index(uint32_t i, uint32_t n, uint32_t key) {
-    uint32_t bits = 2;
-    while ((1u << bits) < n) bits += 2;
-    const uint32_t half = bits >> 1, mask = (1u << half) - 1u;
-    uint32_t x = i;
-    do {
-        uint32_t l = x >> half, r = x & mask;
-#pragma unroll
-        for (uint32_t round = 0; round < 4; ++round) {
-            const uint32_t t = l ^ (feistel_f(r, key, round) & mask);
-            l = r;
-            r = t;
-        }
-        x = (l << half) | r;
-    } while (x >= n);
-    return x;
-}
+using oea::perm_index;      // image of i under the keyed permutation of [0, n) (common.h)
 
 __global__ void link_clear_kernel(uint64_t *keys, int32_t *vals, uint64_t cap) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x) {

@@ -1,14 +1,16 @@
 // nce_half.h -- the sampled-softmax (NCE) half that the ProjE and the ConvE steps share: the two MFMA sweeps, the label rows,
 // the candidate constants and reductions, the step scratch bookkeeping and the fp64 block-partial reduction.  Included by
-// proje_step.hip and conve_step.hip; everything lives in an anonymous namespace (one copy per translation unit).
+// proje_step.hip and conve_step.hip ONLY (its kernels are compiled into whoever includes it); everything lives in an anonymous
+// namespace (one copy per translation unit).  The row helpers and log Q come from row_ops.h.
 #pragma once
-#include "common.h"
+#include "row_ops.h"
 
 #include <algorithm>
 
 namespace {
 
 using oea::grad_t;
+using namespace oea::row;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -21,31 +23,10 @@ constexpr int kTargetWgs = 1024;   // sweep workgroups aimed at (4 per CU)
 constexpr int kMaxSplit = 16;
 constexpr float kBnEps = 1e-3f;
 
-static size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
 static int split_of(int fixed_tiles, int streamed_tiles) {
     int s = (kTargetWgs + fixed_tiles - 1) / fixed_tiles;
     s = std::min(s, std::min(streamed_tiles, kMaxSplit));
     return std::max(s, 1);
-}
-
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float2 load2(const float *row, int dim, int lane) {
-    const int c = 2 * lane;
-    float2 v = make_float2(0.f, 0.f);
-    if (c < dim) {
-        v = *reinterpret_cast<const float2 *>(row + c);
-        if (c + 1 >= dim) v.y = 0.f;
-    }
-    return v;
-}
-__device__ __forceinline__ float dot2(float2 a, float2 b) { return oea::group_sum<64>(fmaf(a.x, b.x, a.y * b.y)); }
-
-// log Q of class c after n tries: Q = -expm1(n log1p(-P)), P = (log(c + 2) - log(c + 1)) / log(E + 1)
-__device__ __forceinline__ double log_q(int64_t c, double n_tries, double inv_log_e1) {
-    const double p = (log((double)(c + 2)) - log((double)(c + 1))) * inv_log_e1;
-    return log(-expm1(n_tries * log1p(-p)));
 }
 
 struct Bufs {

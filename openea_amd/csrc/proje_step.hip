@@ -24,12 +24,6 @@
 
 namespace {
 
-
-constexpr int kSampThreads = 1024;
-constexpr int kSampPer = 4;        // tries per thread and chunk: one Philox call
-constexpr int kSampChunk = kSampThreads * kSampPer;
-
-
 // ---- workspace ---------------------------------------------------------------------------------------------------------------
 struct Layout {
     size_t g_ent, g_rel, g_w, g_b, g_vec;           // dense fp32 gradients (what Adam reads)
@@ -46,7 +40,7 @@ struct Layout {
 static Layout make_layout(int64_t n_ent, int64_t n_rel, int ld, int64_t max_pos, int64_t max_s) {
     Layout L;
     size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return at; };
+    auto take = [&](size_t bytes) { const size_t at = o; o += oea::align256(bytes); return at; };
     const size_t E = (size_t)n_ent, R = (size_t)n_rel, B = (size_t)max_pos, S = (size_t)max_s;
     L.g_ent = take(4 * E * ld); L.g_rel = take(4 * R * ld); L.g_w = take(4 * E * ld); L.g_b = take(4 * E); L.g_vec = take(4 * 4 * LP);
     L.s_ent = take(sizeof(grad_t) * E * ld); L.s_rel = take(sizeof(grad_t) * R * ld); L.s_w = take(sizeof(grad_t) * E * ld);
@@ -69,93 +63,6 @@ static Layout make_layout(int64_t n_ent, int64_t n_rel, int ld, int64_t max_pos,
     return L;
 }
 
-
-// ---- the sampler ---------------------------------------------------------------------------------------------------------------
-
-// One workgroup.  Try t of step s: word t & 3 of Philox(counter = (t >> 2, tag, step), key = seed), u = (w + 0.5) 2^-32, class =
-// the first c with u < T[c].  first[c] holds ~t of the smallest try that drew c (0 = not drawn yet: an unsigned max); a try is a
-// first appearance when first[class] == ~t.  A block scan over the flags numbers the first appearances; the chunk in which their
-// count reaches S ends the draw.  first[] is cleared again on the way out.
-__global__ __launch_bounds__(kSampThreads) void sample_kernel(int64_t n_classes, int n_sampled, uint64_t seed, uint64_t step,
-                                                              const double *__restrict__ thr, int32_t *out_ids, int64_t *out_tries,
-                                                              float *out_logq, uint32_t *first, int32_t *cls, int32_t *status,
-                                                              int64_t max_tries) {
-    __shared__ int wave_tot[kSampThreads / 64];
-    __shared__ int s_found;          // try index that produced the S-th distinct class, -1 while none
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_found = -1;
-    int have = 0;                    // distinct classes seen before this chunk (uniform)
-    int64_t drawn = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < max_tries; base += kSampChunk) {
-        const int64_t t0 = base + (int64_t)tid * kSampPer;
-        const uint4 w4 = oea::philox4x32_10((uint32_t)(t0 >> 2), 0x50726a45u, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-                                            (uint32_t)(seed >> 32));
-        const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-        int32_t c[kSampPer];
-#pragma unroll
-        for (int i = 0; i < kSampPer; ++i) {
-            const double u = ((double)w[i] + 0.5) * 2.3283064365386963e-10;
-            int64_t lo = 0, hi = n_classes - 1;          // first c with u < T[c]; T[E - 1] = 1 > u
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (u < thr[mid]) hi = mid; else lo = mid + 1;
-            }
-            c[i] = (int32_t)lo;
-            if (t0 + i < max_tries) {
-                cls[t0 + i] = c[i];
-                atomicMax(first + lo, ~(uint32_t)(t0 + i));
-            }
-        }
-        drawn = base + kSampChunk < max_tries ? base + kSampChunk : max_tries;
-        __threadfence();
-        __syncthreads();
-        int flag[kSampPer], mine = 0;
-#pragma unroll
-        for (int i = 0; i < kSampPer; ++i) {
-            flag[i] = t0 + i < max_tries && __hip_atomic_load(first + c[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ~(uint32_t)(t0 + i);
-            mine += flag[i];
-        }
-        int incl = mine;             // inclusive scan over the wave, then over the waves
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        int before = have, total = have;
-        for (int wv = 0; wv < kSampThreads / 64; ++wv) {
-            if (wv < wave) before += wave_tot[wv];
-            total += wave_tot[wv];
-        }
-        int rank = before + incl - mine;           // first appearances in front of this thread's tries
-#pragma unroll
-        for (int i = 0; i < kSampPer; ++i) {
-            if (flag[i]) {
-                if (rank < n_sampled) out_ids[rank] = c[i];
-                if (rank == n_sampled - 1) s_found = (int)(t0 + i);
-                ++rank;
-            }
-        }
-        have = total;
-        __syncthreads();
-        if (have >= n_sampled) break;
-    }
-    // leave first[] zeroed
-    for (int64_t t = tid; t < drawn; t += kSampThreads) first[cls[t]] = 0u;
-    const int found = s_found;
-    if (found < 0) {
-        if (tid == 0) *status = 1;
-        return;
-    }
-    const double n_tries = (double)(found + 1), inv = 1.0 / log((double)n_classes + 1.0);
-    if (tid == 0) { *status = 0; *out_tries = found + 1; }
-    __threadfence();
-    __syncthreads();
-    for (int j = tid; j < n_sampled; j += kSampThreads)
-        out_logq[j] = (float)log_q(__hip_atomic_load(out_ids + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), n_tries, inv);
-}
 
 // ---- clearing what the previous gradient phase touched --------------------------------------------------------------------------
 
@@ -338,35 +245,6 @@ static int check_shape(const char *who, int64_t n_ent, int64_t n_rel, int32_t di
 }  // namespace
 
 extern "C" {
-
-size_t oea_log_uniform_workspace_bytes(int64_t n_classes, int64_t n_sampled) {
-    if (n_classes < 1 || n_sampled < 1) return 0;
-    return al(4 * (size_t)n_classes) + al(4 * ((size_t)64 * n_sampled + kSampChunk)) + 256;
-}
-
-int oea_log_uniform_sample(int64_t n_classes, int64_t n_sampled, uint64_t seed, uint64_t step, const double *thresholds,
-                           int32_t *out_ids, int64_t *out_num_tries, float *out_log_q_sampled, void *workspace, void *stream) {
-    OEA_REQUIRE(thresholds && out_ids && out_num_tries && out_log_q_sampled && workspace, "null pointer");
-    OEA_REQUIRE(n_sampled >= 1 && n_sampled <= n_classes, "1 <= n_sampled <= n_classes");
-    OEA_REQUIRE(n_classes < (1LL << 31) && n_sampled < (1LL << 24), "n_classes < 2^31, n_sampled < 2^24");
-    hipStream_t st = oea::as_stream(stream);
-    char *b = static_cast<char *>(workspace);
-    uint32_t *first = reinterpret_cast<uint32_t *>(b);
-    int32_t *cls = reinterpret_cast<int32_t *>(b + al(4 * (size_t)n_classes));
-    int32_t *status = reinterpret_cast<int32_t *>(b + al(4 * (size_t)n_classes) + al(4 * ((size_t)64 * n_sampled + kSampChunk)));
-    sample_kernel<<<1, kSampThreads, 0, st>>>(n_classes, (int)n_sampled, seed, step, thresholds, out_ids, out_num_tries, out_log_q_sampled,
-                                              first, cls, status, 64 * n_sampled);
-    OEA_CHECK_HIP(hipGetLastError());
-    int32_t host_status = 0;
-    OEA_CHECK_HIP(hipMemcpyAsync(&host_status, status, sizeof(host_status), hipMemcpyDeviceToHost, st));
-    OEA_CHECK_HIP(hipStreamSynchronize(st));
-    if (host_status != 0) {
-        oea::set_error("oea_log_uniform_sample: %lld distinct classes of %lld not reached in %lld tries", (long long)n_sampled,
-                       (long long)n_classes, (long long)(64 * n_sampled));
-        return OEA_EUNSUPPORTED;
-    }
-    return OEA_OK;
-}
 
 size_t oea_proje_workspace_floats(int64_t n_ent, int64_t n_rel, int32_t dim, int32_t ld, int64_t max_pos, int64_t max_sampled) {
     if (check_shape("oea_proje_workspace_floats", n_ent, n_rel, dim, ld, max_pos, max_sampled) != OEA_OK) return 0;

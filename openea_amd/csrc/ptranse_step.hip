@@ -36,7 +36,6 @@ using oea::grad_t;
 constexpr int kMaxRel = 2048;             // A and G at 16 MB each
 constexpr int kBlock = 256;
 
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 static int pad4(int64_t n) { return (int)((n + 3) / 4 * 4); }
 
 struct PathWs {
@@ -54,7 +53,7 @@ static size_t path_layout(int64_t n_rel, int32_t ld, void *base, PathWs *ws) {
     const size_t Rp = (size_t)pad4(n_rel);
     char *p = static_cast<char *>(base);
     size_t off = 0;
-    auto take = [&](size_t bytes) { char *q = p ? p + off : nullptr; off += align256(bytes); return q; };
+    auto take = [&](size_t bytes) { char *q = p ? p + off : nullptr; off += oea::align256(bytes); return q; };
     // A^T and the flags first: the region that has to be zero before the first step
     char *at = take(sizeof(grad_t) * Rp * Rp);
     char *ref = take(sizeof(int32_t) * Rp);
@@ -112,7 +111,6 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const float *__restrict__ 
                                                      const int32_t *__restrict__ neg_rel, const float *__restrict__ weight, int64_t n,
                                                      float margin, float path_parm, grad_t *__restrict__ at, int32_t *__restrict__ ref,
                                                      double *loss_accum, const int32_t *err_flag) {
-    __shared__ double wave_loss[kBlock / 64];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     double l = 0.0;
     if (i < n && *err_flag == 0) {
@@ -132,14 +130,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(const float *__restrict__ 
             ref[x] = 1; ref[y] = 1; ref[r] = 1; ref[q] = 1;
         }
     }
-    l = oea::wave_sum_d(l);
-    if ((threadIdx.x & 63) == 0) wave_loss[threadIdx.x >> 6] = l;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(loss_accum, s);
-    }
+    oea::block_loss_add<kBlock / 64>(oea::wave_sum_d(l), threadIdx.x & 63, threadIdx.x >> 6, loss_accum);
 }
 
 #ifdef OEA_DET_SCRATCH
@@ -187,7 +178,6 @@ __device__ __forceinline__ float row_inv_norm(const float *row, int dim, int lan
 }
 
 __global__ __launch_bounds__(kBlock) void weighted_pair_kernel(PairArgs A) {
-    __shared__ double wave_loss[kBlock / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int dim = A.dim;
     double loss_local = 0.0;
@@ -231,42 +221,10 @@ __global__ __launch_bounds__(kBlock) void weighted_pair_kernel(PairArgs A) {
             A.ent_touched[id[3]] = 1; A.rel_touched[id[4]] = 1; A.ent_touched[id[5]] = 1;
         }
     }
-    if (lane == 0) wave_loss[wave] = loss_local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(A.loss_accum, s);
-    }
+    oea::block_loss_add<kBlock / 64>(loss_local, lane, wave, A.loss_accum);
 }
 
 // ---- the epoch's path batches ----------------------------------------------------------------------------------------
-// the keyed permutation of oea_perm_index (link_sampler.hip): 4-round Feistel network on the index bits + cycle walking
-__device__ __forceinline__ uint32_t feistel_f(uint32_t r, uint32_t key, uint32_t round) {
-    uint32_t v = r * 0x9E3779B1u + key + round * 0x85EBCA6Bu;
-    v ^= v >> 15; v *= 0x2C1B3C6Du;
-    v ^= v >> 12; v *= 0x297A2D39u;
-    v ^= v >> 15;
-    return v;
-}
-__device__ __forceinline__ uint32_t perm_index(uint32_t i, uint32_t n, uint32_t key) {
-    uint32_t bits = 2;
-    while ((1u << bits) < n) bits += 2;
-    const uint32_t half = bits >> 1, mask = (1u << half) - 1u;
-    uint32_t x = i;
-    do {
-        uint32_t l = x >> half, r = x & mask;
-#pragma unroll
-        for (uint32_t round = 0; round < 4; ++round) {
-            const uint32_t t = l ^ (feistel_f(r, key, round) & mask);
-            l = r;
-            r = t;
-        }
-        x = (l << half) | r;
-    } while (x >= n);
-    return x;
-}
-
 struct SampleArgs {
     const int32_t *paths[2];     // [n_side, 3]
     const float *w[2];           // [n_side]
@@ -287,7 +245,7 @@ __global__ __launch_bounds__(kBlock) void path_sample_kernel(SampleArgs a) {
         const int side = j < a.num1 ? 0 : 1;
         const uint32_t i = (uint32_t)(side ? j - a.num1 : j);
         const uint4 key = oea::philox4x32_10(a.epoch, step, (uint32_t)side, 0u, a.k0, a.k1);
-        const uint32_t src = perm_index(i, a.n[side], key.x);
+        const uint32_t src = oea::perm_index(i, a.n[side], key.x);
         const uint4 draw = oea::philox4x32_10(a.epoch, step, (uint32_t)side + 2u, i, a.k0, a.k1);
         const int32_t *p = a.paths[side] + 3 * (int64_t)src;
         a.out_paths[3 * t] = p[0];
@@ -296,27 +254,6 @@ __global__ __launch_bounds__(kBlock) void path_sample_kernel(SampleArgs a) {
         a.out_neg[t] = a.rels[side][__umulhi(draw.x, a.nr[side])];
         a.out_w[t] = a.w[side][src];
     }
-}
-
-static int rel_scratch(void *step_workspace, int64_t n_ent, int64_t n_rel, int32_t ld, grad_t **ent_grad, flag_t **ent_touched,
-                       grad_t **rel_grad, flag_t **rel_touched) {
-    // as in oea_semantic_step: entity rows from oea_step_entity_scratch; the relation rows (copy 0) and their flags sit right
-    // in front of the TransH normal-vector scratch
-    void *eg = nullptr, *et = nullptr;
-    int rc = oea_step_entity_scratch(step_workspace, n_ent, n_rel, ld, &eg, &et);
-    if (rc != OEA_OK) return rc;
-    int64_t ng_off = 0, nt_off = 0;
-    rc = oea_step_normal_scratch(n_ent, n_rel, ld, &ng_off, &nt_off);
-    if (rc != OEA_OK) return rc;
-    char *base = static_cast<char *>(step_workspace);
-    *rel_grad = reinterpret_cast<grad_t *>(base + ng_off - align256(sizeof(grad_t) * (size_t)n_rel * ld));
-    *rel_touched = reinterpret_cast<flag_t *>(base + nt_off - align256(sizeof(flag_t) * (size_t)n_rel));
-    OEA_REQUIRE(reinterpret_cast<char *>(*rel_grad) == static_cast<char *>(eg) + align256(sizeof(grad_t) * (size_t)n_ent * ld) &&
-                    reinterpret_cast<char *>(*rel_touched) == static_cast<char *>(et) + align256(sizeof(flag_t) * (size_t)n_ent),
-                "step workspace layout");
-    *ent_grad = static_cast<grad_t *>(eg);
-    *ent_touched = static_cast<flag_t *>(et);
-    return OEA_OK;
 }
 
 static int check_step_cfg(const char *who, const oea_step_cfg *cfg) {
@@ -361,8 +298,7 @@ int oea_path_grad(const float *rel, int64_t n_rel, int32_t dim, int32_t ld, cons
     if (n == 0) return OEA_OK;
     grad_t *ent_grad, *rel_grad;
     flag_t *ent_touched, *rel_touched;
-    rc = rel_scratch(step_workspace, n_ent, n_rel, ld, &ent_grad, &ent_touched, &rel_grad, &rel_touched);
-    if (rc != OEA_OK) return rc;
+    oea::step_scratch_rows(step_workspace, n_ent, n_rel, ld, &ent_grad, &ent_touched, &rel_grad, &rel_touched);
     PathWs ws;
     path_layout(n_rel, ld, path_workspace, &ws);
     const int Rp = pad4(n_rel);
@@ -467,15 +403,11 @@ int oea_weighted_pair_step(float *ent, float *ent_acc, int64_t n_ent, float *rel
     OEA_REQUIRE(ld % 4 == 0, "ld % 4 == 0");
     OEA_REQUIRE(dim > 0 && dim <= ld, "0 < dim <= ld");
     OEA_REQUIRE(n >= 0 && (n == 0 || (pos && neg && weight)), "pos / neg / weight");
-    grad_t *ent_grad, *rel_grad;
-    flag_t *ent_touched, *rel_touched;
-    rc = rel_scratch(step_workspace, n_ent, n_rel, ld, &ent_grad, &ent_touched, &rel_grad, &rel_touched);
-    if (rc != OEA_OK) return rc;
     if (n > 0) {
         PairArgs A;
         A.ent = ent; A.rel = rel; A.ld = ld; A.dim = dim; A.pos = pos; A.neg = neg; A.weight = weight; A.n = n;
         A.margin = cfg->margin; A.ent_l2n = cfg->ent_l2_norm; A.rel_l2n = cfg->rel_l2_norm;
-        A.ent_grad = ent_grad; A.rel_grad = rel_grad; A.ent_touched = ent_touched; A.rel_touched = rel_touched;
+        oea::step_scratch_rows(step_workspace, n_ent, n_rel, ld, &A.ent_grad, &A.ent_touched, &A.rel_grad, &A.rel_touched);
         A.loss_accum = loss_accum;
         const unsigned grid = (unsigned)std::min<int64_t>(oea::ceil_div(n, kBlock / 64), 2048);
         weighted_pair_kernel<<<grid, kBlock, 0, oea::as_stream(stream)>>>(A);

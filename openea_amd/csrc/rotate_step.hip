@@ -40,12 +40,10 @@ struct RotWs {
     __device__ __forceinline__ double *rel_copy(int64_t c) const { return c == 0 ? rel_grad : rel_extra + (c - 1) * rel_stride; }
 };
 
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 static size_t ws_layout(int64_t n_ent2, int64_t n_rel, int32_t ld, void *base, RotWs *ws) {
     size_t off = 0;
     char *b = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return b ? b + o : nullptr; };
+    auto take = [&](size_t bytes) { size_t o = off; off += oea::align256(bytes); return b ? b + o : nullptr; };
     double *eg = (double *)take(sizeof(double) * (size_t)n_ent2 * ld);
     double *rg = (double *)take(sizeof(double) * (size_t)n_rel * ld);
     double *rx = (double *)take(sizeof(double) * (size_t)n_rel * ld * (kRelCopies - 1));

@@ -1,5 +1,6 @@
-// row_ops.h -- the row helpers of the one-wave-per-positive steps (semantic_step.hip, jape_step.hip): a lane holds columns
-// 2 l and 2 l + 1 of a row of up to 128 columns; gradient rows leave the wave through the step engine's scratch.
+// row_ops.h -- the helpers of every kernel that gives a wave one row (semantic_step.hip, jape_step.hip, attr2vec_step.hip, nce_half.h):
+// a lane holds columns 2 l and 2 l + 1 of a row of up to 128 columns; the logistic pair and log Q of the sampled softmax
+// (log_uniform.hip draws under it); gradient rows that leave the wave through the step engine's scratch.
 #pragma once
 #include "common.h"
 
@@ -21,6 +22,15 @@ __device__ __forceinline__ float inv_norm(float2 a, int on) { return on ? rsqrtf
 __device__ __forceinline__ float2 scale2(float2 a, float s) { return make_float2(a.x * s, a.y * s); }
 __device__ __forceinline__ float2 mul2(float2 a, float2 b) { return make_float2(a.x * b.x, a.y * b.y); }
 __device__ __forceinline__ float2 add2(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+// log Q of class c after n tries: Q = -expm1(n log1p(-P)), P = (log(c + 2) - log(c + 1)) / log(E + 1)
+__device__ __forceinline__ double log_q(int64_t c, double n_tries, double inv_log_e1) {
+    const double p = (log((double)(c + 2)) - log((double)(c + 1))) * inv_log_e1;
+    return log(-expm1(n_tries * log1p(-p)));
+}
 
 // one gradient row into the scratch: the lane pairs go through the wave's LDS row so that each atomic instruction covers 64
 // contiguous floats (columns lane and lane + 64)

@@ -55,9 +55,6 @@ struct SemArgs {
     double inv_n;                 // DistMult: 1 / (n_pos + n_neg), the mean over the labelled triples
 };
 
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
 // ---- HolE ------------------------------------------------------------------------------------------------------------
 struct HoleLds {
     float x[kMaxDim];     // rh
@@ -142,7 +139,6 @@ __device__ __forceinline__ HoleRows hole_stage(const SemArgs &A, const int32_t *
 
 __global__ __launch_bounds__(64 * kWaves) void hole_kernel(SemArgs A) {
     __shared__ __attribute__((aligned(16))) HoleLds lds[kWaves];
-    __shared__ double wave_loss[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     HoleLds &L = lds[wave];
     for (int i = lane; i < kY; i += 64) { L.b2[i] = 0.f; L.ah2[i] = 0.f; }
@@ -189,13 +185,7 @@ __global__ __launch_bounds__(64 * kWaves) void hole_kernel(SemArgs A) {
         se.flush(A.ent_grad, A.ent_touched, A.ld, dim, lane, L.buf);
         sr.flush(A.rel_grad, A.rel_touched, A.ld, dim, lane, L.buf);
     }
-    if (lane == 0) wave_loss[wave] = loss_local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kWaves; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(A.loss_accum, s);
-    }
+    oea::block_loss_add<kWaves>(loss_local, lane, wave, A.loss_accum);
 }
 
 // ---- SimplE ----------------------------------------------------------------------------------------------------------
@@ -221,7 +211,6 @@ __device__ __forceinline__ Term simple_term(const SemArgs &A, int64_t ea, int64_
 
 __global__ __launch_bounds__(64 * kWaves) void simple_kernel(SemArgs A) {
     __shared__ __attribute__((aligned(16))) float buf[kWaves][kMaxDim];
-    __shared__ double wave_loss[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t E = A.ent_half, R = A.rel_half;
     const int k = A.k;
@@ -254,13 +243,7 @@ __global__ __launch_bounds__(64 * kWaves) void simple_kernel(SemArgs A) {
         se.flush(A.ent_grad, A.ent_touched, A.ld, A.dim, lane, buf[wave]);
         sr.flush(A.rel_grad, A.rel_touched, A.ld, A.dim, lane, buf[wave]);
     }
-    if (lane == 0) wave_loss[wave] = loss_local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kWaves; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(A.loss_accum, s);
-    }
+    oea::block_loss_add<kWaves>(loss_local, lane, wave, A.loss_accum);
 }
 
 // ---- DistMult --------------------------------------------------------------------------------------------------------
@@ -268,7 +251,6 @@ __global__ __launch_bounds__(64 * kWaves) void simple_kernel(SemArgs A) {
 // With h == t both halves land in the same slot.
 __global__ __launch_bounds__(64 * kWaves) void distmult_kernel(SemArgs A) {
     __shared__ __attribute__((aligned(16))) float buf[kWaves][kMaxDim];
-    __shared__ double wave_loss[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int k = A.k;
     const float inv_n = (float)A.inv_n;
@@ -298,16 +280,8 @@ __global__ __launch_bounds__(64 * kWaves) void distmult_kernel(SemArgs A) {
         se.flush(A.ent_grad, A.ent_touched, A.ld, A.dim, lane, buf[wave]);
         sr.flush(A.rel_grad, A.rel_touched, A.ld, A.dim, lane, buf[wave]);
     }
-    if (lane == 0) wave_loss[wave] = loss_local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kWaves; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(A.loss_accum, s * A.inv_n);
-    }
+    oea::block_loss_add<kWaves>(loss_local, lane, wave, A.loss_accum, A.inv_n);
 }
-
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -339,21 +313,6 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
     }
     if (model == OEA_SEMANTIC_SIMPLE)
         OEA_REQUIRE(n_ent % 2 == 0 && n_rel % 2 == 0, "SimplE: stacked tables, ent = [H; T] (2E rows), rel = [R1; R2] (2R rows)");
-    // the step engine's scratch, as in oea_transr_step: entity rows from oea_step_entity_scratch; the relation rows (copy 0)
-    // and their flags sit right in front of the TransH normal-vector scratch (include/openea_hip.h: [ent_grad | rel_grad |
-    // nrm_grad | ent_touched | rel_touched | nrm_touched], each region 256-byte aligned)
-    void *eg = nullptr, *et = nullptr;
-    int rc = oea_step_entity_scratch(step_workspace, n_ent, n_rel, ld, &eg, &et);
-    if (rc != OEA_OK) return rc;
-    int64_t ng_off = 0, nt_off = 0;
-    rc = oea_step_normal_scratch(n_ent, n_rel, ld, &ng_off, &nt_off);
-    if (rc != OEA_OK) return rc;
-    char *base = static_cast<char *>(step_workspace);
-    grad_t *rel_grad = reinterpret_cast<grad_t *>(base + ng_off - align256(sizeof(grad_t) * (size_t)n_rel * ld));
-    flag_t *rel_touched = reinterpret_cast<flag_t *>(base + nt_off - align256(sizeof(flag_t) * (size_t)n_rel));
-    OEA_REQUIRE(reinterpret_cast<char *>(rel_grad) == static_cast<char *>(eg) + align256(sizeof(grad_t) * (size_t)n_ent * ld) &&
-                    reinterpret_cast<char *>(rel_touched) == static_cast<char *>(et) + align256(sizeof(flag_t) * (size_t)n_ent),
-                "step workspace layout");
     hipStream_t st = oea::as_stream(stream);
     if (n_pos > 0) {
         SemArgs A;
@@ -362,8 +321,7 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
         A.rel_half = model == OEA_SEMANTIC_SIMPLE ? n_rel / 2 : n_rel;
         A.pos = pos; A.neg = neg; A.n_pos = n_pos; A.k = (int)k;
         A.margin = cfg->margin; A.ent_l2n = cfg->ent_l2_norm; A.rel_l2n = cfg->rel_l2_norm;
-        A.ent_grad = static_cast<grad_t *>(eg); A.rel_grad = rel_grad;
-        A.ent_touched = static_cast<flag_t *>(et); A.rel_touched = rel_touched;
+        oea::step_scratch_rows(step_workspace, n_ent, n_rel, ld, &A.ent_grad, &A.ent_touched, &A.rel_grad, &A.rel_touched);
         A.loss_accum = loss_accum;
         A.inv_n = 1.0 / (double)(n_pos + n_neg);
         const unsigned grid = (unsigned)std::min<int64_t>(oea::ceil_div(n_pos, kWaves), kMaxBlocks);

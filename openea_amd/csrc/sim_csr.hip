@@ -100,7 +100,6 @@ __device__ __forceinline__ void load_l2n(const float *row, int dim, int lane, do
 }
 
 __global__ __launch_bounds__(64 * kWaves) void sim_loss_kernel(SimLossArgs A) {
-    __shared__ double wave_loss[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double loss_local = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kWaves + wave; i < A.m; i += (int64_t)gridDim.x * kWaves) {
@@ -118,13 +117,7 @@ __global__ __launch_bounds__(64 * kWaves) void sim_loss_kernel(SimLossArgs A) {
         const double dx = ax - tx * inv, dy = ay - ty * inv;
         loss_local += oea::wave_sum_d(dx * dx + dy * dy);
     }
-    if (lane == 0) wave_loss[wave] = loss_local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kWaves; ++w) s += wave_loss[w];
-        if (s != 0.0) atomicAdd(A.loss_accum, A.beta * s);
-    }
+    oea::block_loss_add<kWaves>(loss_local, lane, wave, A.loss_accum, A.beta);
 }
 
 // one pass over the row blocks of e1: similarity into block_buf, then the counting or the filling kernel

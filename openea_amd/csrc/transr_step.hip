@@ -36,8 +36,6 @@ constexpr int T = 64;            // items per tile
 constexpr int SB = 256;          // items per block of the sort
 constexpr int kMaxDim = 128;
 
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct TrWs {
     int32_t *hist;       // [nb][n_rel]: block histogram, then the block's offset per relation
     int32_t *rank;       // [N]
@@ -59,7 +57,7 @@ static size_t tr_layout(int64_t n_rel, int32_t dim, int64_t n_pos, void *base, T
     const int64_t N = 4 * n_pos, nb = oea::ceil_div(N, SB), mt = max_tiles(N, n_rel), dp = dpad(dim);
     size_t off = 0;
     char *b = static_cast<char *>(base);
-    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return b ? b + o : nullptr; };
+    auto take = [&](size_t bytes) { size_t o = off; off += oea::align256(bytes); return b ? b + o : nullptr; };
     TrWs w;
     w.hist = (int32_t *)take(sizeof(int32_t) * (size_t)(nb * n_rel));
     w.rank = (int32_t *)take(sizeof(int32_t) * (size_t)N);
@@ -466,23 +464,12 @@ int oea_transr_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float
         return OEA_EUNSUPPORTED;
     }
     OEA_REQUIRE(4 * n_pos < (int64_t)1 << 31, "4 n_pos < 2^31");
-    // the step engine's scratch: entity rows from oea_step_entity_scratch; the relation rows (copy 0) and their flags sit right
-    // in front of the TransH normal-vector scratch (include/openea_hip.h: [ent_grad | rel_grad | nrm_grad | ent_touched |
-    // rel_touched | nrm_touched], each region 256-byte aligned)
-    void *eg = nullptr, *et = nullptr;
-    int rc = oea_step_entity_scratch(step_workspace, n_ent, n_rel, ld, &eg, &et);
-    if (rc != OEA_OK) return rc;
-    int64_t ng_off = 0, nt_off = 0;
-    rc = oea_step_normal_scratch(n_ent, n_rel, ld, &ng_off, &nt_off);
-    if (rc != OEA_OK) return rc;
-    char *base = static_cast<char *>(step_workspace);
-    grad_t *rel_grad = reinterpret_cast<grad_t *>(base + ng_off - align256(sizeof(grad_t) * (size_t)n_rel * ld));
-    flag_t *rel_touched = reinterpret_cast<flag_t *>(base + nt_off - align256(sizeof(flag_t) * (size_t)n_rel));
-    OEA_REQUIRE(reinterpret_cast<char *>(rel_grad) == static_cast<char *>(eg) + align256(sizeof(grad_t) * (size_t)n_ent * ld) &&
-                    reinterpret_cast<char *>(rel_touched) == static_cast<char *>(et) + align256(sizeof(flag_t) * (size_t)n_ent),
-                "step workspace layout");
     hipStream_t st = oea::as_stream(stream);
     if (n_pos > 0 && n_rel > 0) {
+        int rc = OEA_OK;
+        grad_t *ent_grad, *rel_grad;
+        flag_t *ent_touched, *rel_touched;
+        oea::step_scratch_rows(step_workspace, n_ent, n_rel, ld, &ent_grad, &ent_touched, &rel_grad, &rel_touched);
         TrWs ws;
         tr_layout(n_rel, dim, n_pos, transr_workspace, &ws);
         const int64_t N = 4 * n_pos, nb = oea::ceil_div(N, SB), mt = max_tiles(N, n_rel);
@@ -491,8 +478,6 @@ int oea_transr_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float
         rank_kernel<<<(unsigned)nb, SB, 0, st>>>(pos, neg, N, n_rel, ws.hist, ws.rank);
         scan_kernel<<<1, 1024, 0, st>>>(ws.hist, nb, n_rel, ws.rel_tile0, ws.rel_ntiles, ws.n_tiles, ws.tiles, T);
         scatter_kernel<<<(unsigned)nb, SB, 0, st>>>(pos, neg, N, n_rel, ws.hist, ws.rank, ws.sorted);
-        grad_t *ent_grad = static_cast<grad_t *>(eg);
-        flag_t *ent_touched = static_cast<flag_t *>(et);
 #define OEA_TILES(DP, WHICH) rc = launch_tiles<DP>(ent, ld, dim, *cfg, rel_matrix, rel_matrix_acc, pos, neg, ws, (unsigned)mt, ent_grad, \
                                                    ent_touched, WHICH, st)
 #define OEA_TR_DISPATCH(WHICH)                                                                 \

@@ -38,6 +38,7 @@
 
 namespace {
 
+using oea::align256;
 using oea::group_sum;
 
 using oea::flag_t;
@@ -67,8 +68,6 @@ constexpr int kMaxBlocks = 4096;
 // The relation scratch is therefore replicated kRelCopies times; a work item adds into copy
 // (item index % kRelCopies) and apply_rows sums the copies.
 constexpr int kRelCopies = 16;
-
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 static size_t ws_layout(int64_t n_ent, int64_t n_rel, int32_t ld, void *base, StepWs *ws) {
     size_t off = 0;
@@ -2417,6 +2416,13 @@ static int for_apply_width(int64_t n_ent, int64_t n_rel, int32_t ld, F &&f) {
 }
 
 }  // namespace
+
+void oea::step_scratch_rows(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, grad_t **ent_grad, flag_t **ent_touched,
+                            grad_t **rel_grad, flag_t **rel_touched) {
+    StepWs ws;
+    ws_layout(n_ent, n_rel, ld, workspace, &ws);
+    *ent_grad = ws.ent_grad; *ent_touched = ws.ent_touched; *rel_grad = ws.rel_grad; *rel_touched = ws.rel_touched;
+}
 
 #define OEA_TRY_RC(...) do { const int _rc = (__VA_ARGS__); if (_rc != OEA_OK) return _rc; } while (0)
 

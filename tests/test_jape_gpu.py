@@ -46,6 +46,36 @@ def test_sample_steps_equal_the_single_step_sampler(n_classes, n_sampled):
     assert len({tuple(r) for r in ids.cpu().numpy().tolist()}) == steps
 
 
+def test_sampler_failure_path_and_last_chunk():
+    """n_classes = n_sampled = 8192 (the LDS limit): every class has to appear within 64 * 8192 tries = 128 chunks.  With this seed
+    steps 1 and 2 get there (in the late chunks) and steps 3 and 4 miss one class: both ends of both kernels."""
+    from openea_amd import ops
+    from openea_amd._lib import OpenEAHipError
+    from test_proje_cpu import classes_of, sampler_words, thresholds
+    dev = ops.device()
+    n, seed = ops.LOG_UNIFORM_STEPS_MAX_CLASSES, 20190719
+    assert n == 8192
+    assert len(np.unique(classes_of(sampler_words(seed, 3, 64 * n), thresholds(n)))) == n - 1      # the restatement itself misses one
+    ref = {s: log_uniform_reference(n, n, seed, s) for s in (1, 2)}
+    single = ops.LogUniformSampler(n, n, seed, dev)
+    ids, tries, logq, status = ops.log_uniform_sample_steps(n, n, seed, 1, 4, single.thresholds)
+    torch.cuda.synchronize()
+    assert status.cpu().tolist() == [0, 0, 1, 1]
+    for row, s in enumerate((1, 2)):
+        ref_ids, ref_tries, ref_lq = ref[s]
+        assert np.array_equal(ids[row].cpu().numpy(), ref_ids) and int(tries[row]) == ref_tries, s
+        assert np.abs(logq[row].cpu().numpy().astype(np.float64) - ref_lq).max() <= 1e-6, s
+    for row in (2, 3):
+        assert torch.equal(ids[row], torch.arange(n, dtype=torch.int32, device=dev)), row
+        assert int(logq[row].count_nonzero()) == 0 and int(tries[row]) == 1, row
+    with pytest.raises(OpenEAHipError):
+        single.sample(3)
+    assert int(single.workspace.view(torch.int32)[:n].count_nonzero()) == 0       # a failed draw clears the table all the same
+    i2, t2, q2 = single.sample(2)
+    assert np.array_equal(i2.cpu().numpy(), ref[2][0]) and int(t2.item()) == ref[2][1]
+    assert np.abs(q2.cpu().numpy().astype(np.float64) - ref[2][2]).max() <= 1e-6
+
+
 def test_sample_steps_refuse_more_classes_than_fit():
     from openea_amd import ops
     from openea_amd._lib import OpenEAHipError

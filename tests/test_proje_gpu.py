@@ -1,4 +1,4 @@
-"""ProjE on the device (csrc/proje_step.hip): the log-uniform sampler against its numpy restatement, the gradient phase of
+"""ProjE on the device (csrc/proje_step.hip): the log-uniform sampler (csrc/log_uniform.hip) against its numpy restatement, the gradient phase of
 oea_proje_step against the reference's own graph (tests/golden/proje_graph.npz) and against the float64 restatement of
 test_proje_cpu.py at the shapes that have tails, three Adam steps at the EN-FR-15K-V1 batch shape, run to run in the fixed-point
 build, the configurations the step refuses, and the model class end to end."""
