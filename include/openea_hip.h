@@ -338,6 +338,48 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
 int oea_jape_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim, int32_t ld,
                   const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg, float neg_alpha, const oea_step_cfg *cfg,
                   void *step_workspace, double *loss_accum, void *stream);
+/* AttrE's character step (approaches/attre.py:88-109, 166-187; csrc/attre_step.hip), one wave per positive (e, a, v) and its
+ * k = cfg->neg_group_k head-corrupted negatives (e', a, v), e' = neg_heads[p k .. p k + k):
+ *   ue = l2n?(ent_ce)[e], wa = l2n?(attr)[a], v = sum_p w_p l2n?(chars)[value_chars[v, p]], w_p = sum_{m = p + 1 .. L} 1 / m,
+ *   score = |ue + wa - v|^2 (cfg->l1: |.|_1), loss = cfg->loss_kind, one of margin-based (k == 1), limited, logistic (losses.py).
+ * ent_ce is the step engine's entity table and attr its relation table: cfg->ent_l2_norm / rel_l2_norm (= attr_l2_norm) / opt_kind
+ * (SGD or Adagrad) / lr, step_workspace as for oea_triple_step with (n_ent, n_attr), and the call ends with
+ * oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY).  The character table [n_chars, ld] (normalised by char_l2_norm) gets its
+ * gradient without row atomics from every positive: the scoring kernel stores dL/dv per positive, a second kernel sums
+ * w_i dL/dv[p] per character -- char_path 0: in LDS slabs of [n_chars, ld] while n_chars <= oea_attre_lds_chars(ld), n_slabs
+ * workgroups (0: one per 16 positives, at most one per CU; never above 512) each writing a partial; else by atomic row adds into one dense buffer; 1 / 2
+ * force the LDS / the atomic path -- and a closing kernel adds the partials in a fixed order, goes back through the normalisation
+ * (clamp 1e-12) and runs SGD or Adagrad (char_acc, initial value 0.1) on the n_chars rows.  value_chars int32 [n_values, literal_len]
+ * (id 0: padding, a trained row); pos int32 [n_pos, 3] = (entity, attribute, row of value_chars).  char_workspace:
+ * oea_attre_char_workspace_bytes(n_chars, ld, n_pos) bytes or more, no initial value.  A check kernel runs first: a character id
+ * outside [0, n_chars) sets bit 1 of *err_flag (device int32, zeroed by the caller), a value, entity or attribute id outside its
+ * table bit 2, and with the flag set nothing is written.  loss_accum += the batch sum.  Adam / Adadelta, dim > 128:
+ * OEA_EUNSUPPORTED; n_neg != k n_pos, margin-based with k != 1, another loss_kind, ld % 4 != 0, literal_len outside 1..32, char_path 1
+ * with a slab that does not fit, a workspace too small, a null pointer: OEA_EINVAL -- both before anything is launched. */
+int64_t oea_attre_lds_chars(int32_t ld);
+size_t oea_attre_char_workspace_bytes(int64_t n_chars, int32_t ld, int64_t max_pos);
+int oea_attre_char_step(float *ent_ce, float *ent_acc, int64_t n_ent, float *attr, float *attr_acc, int64_t n_attr, float *chars,
+                        float *char_acc, int64_t n_chars, int32_t dim, int32_t ld, const int32_t *value_chars, int64_t n_values,
+                        int32_t literal_len, const int32_t *pos, int64_t n_pos, const int32_t *neg_heads, int64_t n_neg,
+                        int32_t char_l2_norm, int32_t char_path, int32_t n_slabs, const oea_step_cfg *cfg, void *step_workspace,
+                        void *char_workspace, size_t char_workspace_bytes, int32_t *err_flag, double *loss_accum, void *stream);
+/* AttrE's negatives (generate_neg_attribute_triples, batch.py:187-199): only the head is corrupted, and with a value id of its own
+ * per triple the reference's redraw rejects exactly e' == e.  out[p k + s] = entity_list[j], j uniform over the list's positions
+ * without ent_pos[head of p] (ent_pos int32 [n_ent]: position in the side's list, -1 elsewhere), from Philox4x32-10 with counter
+ * (p + pos_offset, step, 0, s) keyed by the seed: a pure function of (seed, step, position).  Positives [0, n_split) draw from side
+ * 0, the rest from side 1.  out: device int32 [n_pos k].  A side in use with n_ent_list < 2 (the reference would spin), k < 1, a
+ * null pointer: OEA_EINVAL before any launch. */
+int oea_attre_sample_heads(const int32_t *pos, int64_t n_pos, int64_t n_split, int32_t k, const int32_t *entity_list0, int32_t n_ent_list0,
+                           const int32_t *ent_pos0, const int32_t *entity_list1, int32_t n_ent_list1, const int32_t *ent_pos1,
+                           int64_t n_ent, uint64_t seed, uint32_t step, uint32_t pos_offset, int32_t *out, void *stream);
+/* `steps` joint steps of AttrE (attre.py:189-191, 221-233) in one pass: loss = sum_e (1 - l2n?(ent)[e] . l2n?(ent_ce)[e]) over the
+ * WHOLE entity list in every step, so a wave holds row e of both tables over the steps (SGD, or Adagrad with the two accumulators of
+ * this optimiser instance) and stores once; the tables equal `steps` calls with steps = 1 bit for bit.  row_count int32 [n_ent]: how
+ * often the list names row e (under the sharing alignment a training pair is one id in both KGs' lists: 2; 0: the row stays), its
+ * term and gradient times that; NULL: every row once.  loss_accum: device double [steps], loss_accum[s] += the loss of step s.  Adam / Adadelta, dim > 128: OEA_EUNSUPPORTED; ld % 4 != 0, n_ent < 1, steps < 1, a
+ * null pointer: OEA_EINVAL -- both before any launch. */
+int oea_attre_joint_epoch(float *ent, float *ent_acc, float *ent_ce, float *ent_ce_acc, const int32_t *row_count, int64_t n_ent, int32_t dim,
+                          int32_t ld, int32_t ent_l2_norm, int32_t opt_kind, float lr, int32_t steps, double *loss_accum, void *stream);
 /* m distinct elements of [0, n) (random.sample(range(n), m), attr2vec.py:150 / jape.py:134): out[i] = pi(i), i < m, with pi a
  * bijection of [0, n) that is a pure function of (seed, step) -- a 6-round Feistel network over max(2, ceil(log2 n)) bits, cycle
  * walked into [0, n), its round keys from Philox4x32-10(counter = (step lo, step hi, 0x64697374, 0 | 1), key = (seed lo, seed hi))

@@ -195,6 +195,12 @@ PROTOTYPES = {
     "oea_semantic_step": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
                                     _vp, _vp, _vp]),
     "oea_jape_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _f32, C.POINTER(StepCfg), _vp, _vp, _vp]),
+    "oea_attre_lds_chars": (_i64, [_i32]),
+    "oea_attre_char_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "oea_attre_char_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,
+                                      _i32, _i32, _i32, C.POINTER(StepCfg), _vp, _vp, _sz, _vp, _vp, _vp]),
+    "oea_attre_sample_heads": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _u64, _u32, _u32, _vp, _vp]),
+    "oea_attre_joint_epoch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "oea_sample_distinct": (C.c_int, [_i64, _i64, _u64, _u64, _vp, _vp]),
     "oea_sim_csr_count": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _f32, _i64, _vp, _vp, _vp]),
     "oea_sim_csr_fill": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),

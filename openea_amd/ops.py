@@ -321,6 +321,69 @@ def jape_step(ent, ent_acc, rel, rel_acc, dim, pos, neg, neg_alpha, cfg, workspa
                               _stream()))
 
 
+# ---- AttrE ------------------------------------------------------------------------------------------------------
+ATTRE_MAX_DIM = 128
+ATTRE_MAX_LITERAL_LEN = 32
+ATTRE_PATH_AUTO, ATTRE_PATH_LDS, ATTRE_PATH_ATOMIC = 0, 1, 2
+
+
+def attre_lds_chars(ld):
+    """the largest character table [C, ld] whose gradient slab the character step still sums in LDS (oea_attre_lds_chars; half as
+    many in the deterministic build, whose slab holds int64)"""
+    return int(lib().oea_attre_lds_chars(int(ld)))
+
+
+def attre_char_workspace(n_chars, ld, max_pos, dev=None):
+    nbytes = lib().oea_attre_char_workspace_bytes(int(n_chars), int(ld), int(max_pos))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev or device())
+
+
+def attre_check(err_flag):
+    """what the check kernel of attre_char_step found in device memory (reads the flag: a host wait)"""
+    e = int(err_flag.item())
+    if e:
+        raise OpenEAHipError("AttrE's character step refused its device arguments (nothing was written):%s%s"
+                             % (" a character id lies outside the character table;" if e & 1 else "",
+                                " a value, entity or attribute id lies outside its table" if e & 2 else ""))
+
+
+def attre_char_step(ent_ce, ent_acc, attr, attr_acc, chars, char_acc, dim, value_chars, pos, neg_heads, char_l2_norm, cfg, workspace,
+                    char_ws, err_flag, loss_accum, char_path=ATTRE_PATH_AUTO, n_slabs=0):
+    """One character step of AttrE in place (oea_attre_char_step): pos int32 [n, 3] = (entity, attribute, row of value_chars),
+    neg_heads int32 [n * k] with neg_heads[p*k:(p+1)*k] the corrupted heads of pos p, k = cfg.neg_group_k; value_chars int32
+    [n_values, literal_len]; the batch sum is added to `loss_accum`.  err_flag: device int32 [1], zeroed (attre_check reads it)."""
+    n_neg = 0 if neg_heads is None else neg_heads.numel()
+    check(lib().oea_attre_char_step(_p(ent_ce), _p(ent_acc), ent_ce.shape[0], _p(attr), _p(attr_acc), attr.shape[0], _p(chars),
+                                    _p(char_acc), chars.shape[0], dim, ent_ce.shape[1], _p(value_chars), value_chars.shape[0],
+                                    value_chars.shape[1], _p(pos), pos.shape[0], _p(neg_heads), n_neg, int(bool(char_l2_norm)),
+                                    int(char_path), int(n_slabs), C.byref(cfg), _p(workspace), _p(char_ws), char_ws.numel(),
+                                    _p(err_flag), _p(loss_accum), _stream()))
+
+
+def attre_sample_heads(pos, n_split, k, entity_list0, ent_pos0, entity_list1, ent_pos1, seed, step, pos_offset=0, out=None):
+    """head-only negatives of AttrE's attribute triples (oea_attre_sample_heads): rows [0, n_split) of pos draw from entity_list0,
+    the rest from entity_list1, never the positive's own head -> device int32 [n * k]"""
+    n = pos.shape[0]
+    if out is None:
+        out = torch.empty(n * k, dtype=torch.int32, device=pos.device)
+    assert out.dtype == torch.int32 and out.numel() >= n * k
+    n_ent = (ent_pos0 if ent_pos0 is not None else ent_pos1).numel()
+    check(lib().oea_attre_sample_heads(_p(pos), n, int(n_split), int(k), _p(entity_list0),
+                                       0 if entity_list0 is None else entity_list0.numel(), _p(ent_pos0), _p(entity_list1),
+                                       0 if entity_list1 is None else entity_list1.numel(), _p(ent_pos1), n_ent,
+                                       int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(pos_offset) & 0xFFFFFFFF, _p(out), _stream()))
+    return out[:n * k]
+
+
+def attre_joint_epoch(ent, ent_acc, ent_ce, ent_ce_acc, dim, ent_l2_norm, optimizer, lr, steps, loss_accum, row_count=None):
+    """`steps` joint steps of AttrE in one pass over both entity tables (oea_attre_joint_epoch); loss_accum: device f64 [steps];
+    row_count: device int32 [rows], how often the step's entity list names a row (None: once each)"""
+    assert loss_accum.dtype == torch.float64 and loss_accum.numel() >= steps
+    assert row_count is None or (row_count.dtype == torch.int32 and row_count.numel() == ent.shape[0])
+    check(lib().oea_attre_joint_epoch(_p(ent), _p(ent_acc), _p(ent_ce), _p(ent_ce_acc), _p(row_count), ent.shape[0], dim, ent.shape[1],
+                                      int(bool(ent_l2_norm)), OPT_KIND[optimizer], float(lr), int(steps), _p(loss_accum), _stream()))
+
+
 def sample_distinct(n, m, seed, step, out=None, dev=None):
     """m distinct elements of [0, n) as a pure function of (seed, step) (oea_sample_distinct) -> device int32 [m]"""
     if out is None:

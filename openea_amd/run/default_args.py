@@ -1,6 +1,6 @@
 """Hyper-parameter sets of the approaches on the hot path, as python dicts.
 
-The values are the ones the reference ships in run/args/{mtranse,bootea,aligne,gcnalign,transh,transd,hole,simple,rotate,iptranse,proje,conve,jape,imuse,...}_args_{15K,100K}.json
+The values are the ones the reference ships in run/args/{mtranse,bootea,aligne,gcnalign,transh,transd,hole,simple,rotate,iptranse,proje,conve,jape,imuse,attre,...}_args_{15K,100K}.json
 (the `args_*` API: one attribute per key).  ``get_args(name, scale)`` returns an ``ARGs`` object that any
 model accepts through ``set_args``; a reference JSON file loaded with ``load_args`` works the same way.
 """
@@ -81,6 +81,11 @@ _ARGS = {
                   loss_norm="L2", margin=1.5, loss="margin-based", neg_sampling="uniform", neg_triple_num=1, learning_rate=0.01,
                   optimizer="SGD", batch_size=5000, start_valid=10, eval_metric="inner", eval_norm=True, sim_thresholds_ent=0.6,
                   sim_thresholds_attr=0.6, interactive_model_iter_num=1),
+    # run/args/attre_args_15K.json
+    "AttrE": dict(embedding_module="AttrE", alignment_module="sharing", dim=100, init="normal", ent_l2_norm=True, rel_l2_norm=True,
+                  attr_l2_norm=True, char_l2_norm=True, loss_norm="L2", margin=1.5, loss="margin-based", neg_sampling="uniform",
+                  neg_triple_num=1, learning_rate=0.01, optimizer="SGD", batch_size=5000, eval_metric="inner", eval_norm=True,
+                  literal_len=5),
     "GCN_Align": dict(embedding_module="GCN_Align", alignment_module="mapping", dim=100, neg_sampling="uniform",
                       neg_triple_num=5, learning_rate=8, batch_size=5000, test_threads_num=3, eval_metric="manhattan",
                       eval_norm=False, support_number=1, se_dim=100, ae_dim=100, hidden1=100, gamma=3,
@@ -115,6 +120,7 @@ _SCALE_100K = {
     "ConvE": dict(batch_size=5000, batch_threads_num=3, test_threads_num=10, start_valid=300),
     "JAPE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
     "IMUSE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10, start_valid=100),
+    "AttrE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
     "GCN_Align": dict(batch_size=20000, learning_rate=25),
     "AliNet": dict(batch_size=20000, truncated_epsilon=0.995, min_rel_win=15),
     "RDGCN": dict(batch_size=20000, learning_rate=0.001, start_valid=50),
