@@ -338,6 +338,50 @@ int oea_semantic_step(int32_t model, float *ent, float *ent_acc, int64_t n_ent, 
 int oea_jape_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *rel_acc, int64_t n_rel, int32_t dim, int32_t ld,
                   const int32_t *pos, int64_t n_pos, const int32_t *neg, int64_t n_neg, float neg_alpha, const oea_step_cfg *cfg,
                   void *step_workspace, double *loss_accum, void *stream);
+/* ---- MultiKE (approaches/multi_ke.py; csrc/multike_step.hip) ------------------------------------------------------------------
+ * oea_multike_cnn_step: the attribute CNN (multi_ke.py:154-176) on a batch of n positives (entity, attribute, literal), int32
+ * [n, 3].  attr [n_attr, ld] is read raw, lit [n_lit, ld] is constant, a net's entity table [n_ent, ld] is read through the row
+ * normalisation when ent_l2_norm is set.  With c = 1 / sqrt(1 + 1e-3):
+ *   x = (a ; v) gamma c + beta;  z1 = tanh(conv(x, K1[2,4,1,2]) + b1);  z2 = tanh(conv(z1, K2[2,4,2,2]) + b2)   ('same': rows padded
+ *   (0, 1), columns (1, 2));  n = z2 / max(|z2| along the width, 1e-6);  t = tanh(flat(n) . W[4 dim, ld] + bd), flat in the order
+ *   (row, column, channel);  y = t / max(|t|_F over the whole batch, 1e-6);  loss = factor sum_b w_b softplus(|h_b - y_b|^2),
+ *   w_b = attr_weight[attribute of b] for a weighted net, 1 otherwise.
+ * n_nets = 1 or 2 nets share the batch; p = gamma [dim], beta [dim], K1 [16], b1 [2], K2 [32], b2 [2], W [4 dim, ld], bd [dim].
+ * The gradients w.r.t. the normalised entity rows go into the entity rows of the net's own step workspace (oea_step_workspace_bytes
+ * (n_ent, n_rel_ws, ld)), those w.r.t. the attribute rows of ALL nets into the relation rows of net 0's (n_rel_ws == n_attr there):
+ * oea_triple_step_phase(..., n_pos = 0, OEA_PHASE_APPLY) on each finishes the step.  OEA_PHASE_GRAD leaves the eight parameter
+ * gradients of net k readable through oea_multike_cnn_grads (same order; W with stride ld); OEA_PHASE_BOTH also runs SGD with lr on
+ * the parameters.  Everything summed over the batch is an fp64 partial per workgroup added in a fixed order.
+ * workspace: oea_multike_cnn_workspace_bytes(dim, ld, max_n) bytes for n <= max_n, no initialisation needed.  loss_accum += the loss
+ * of all nets.  dim > 128: OEA_EUNSUPPORTED; ld % 4 != 0, n < 1, n > max_n, a null pointer, OEA_PHASE_APPLY: OEA_EINVAL -- both before
+ * anything is launched.  ids are not checked on the device.  One GPU. */
+typedef struct oea_multike_net {
+    float *p[8];
+    const float *ent;
+    void *step_workspace;
+    int64_t n_rel_ws;
+    int32_t weighted;
+    int32_t ent_l2_norm;
+    float factor;
+} oea_multike_net;
+size_t oea_multike_cnn_workspace_bytes(int32_t dim, int32_t ld, int64_t max_n);
+int oea_multike_cnn_grads(void *workspace, int32_t dim, int32_t ld, int64_t max_n, int32_t net, void **grads);
+int oea_multike_cnn_step(const oea_multike_net *nets, int32_t n_nets, int64_t n_ent, const float *attr, int64_t n_attr,
+                         const float *lit, int64_t n_lit, int32_t dim, int32_t ld, const int32_t *batch, int64_t n,
+                         const float *attr_weight, float lr, void *workspace, int64_t max_n, double *loss_accum, int32_t phase,
+                         void *stream);
+/* oea_multike_rows: the row-wise terms of MultiKE's other views, one wave per item, gradients w.r.t. the (normalised) rows into
+ * the step workspaces ws_a (n_ent, n_rel_a) of table_a and ws_b (n_ent, n_rel_b) of table_b:
+ *   OEA_MULTIKE_ROWS_CROSS  coef |A[h] + rel[r] - B[t]|^2                         items int32 [n, 3]
+ *   OEA_MULTIKE_ROWS_PULL   coef |A[e] - B[e]|^2                                  items int32 [n]; ws_b NULL: B is constant
+ *   OEA_MULTIKE_ROWS_WSOFT  coef rel_weight[r] softplus(|A[h] + rel[r] - B[t]|^2)  items int32 [n, 3]
+ * The relation rows' gradients go into the relation rows of ws_a (rel_side 0) or ws_b (rel_side 1).  An id that repeats counts as
+ * often.  loss_accum += the sum.  n == 0 launches nothing.  dim > 128: OEA_EUNSUPPORTED; ld % 4 != 0, a null pointer: OEA_EINVAL. */
+enum { OEA_MULTIKE_ROWS_CROSS = 0, OEA_MULTIKE_ROWS_PULL = 1, OEA_MULTIKE_ROWS_WSOFT = 2 };
+int oea_multike_rows(int32_t kind, const float *table_a, void *ws_a, int64_t n_rel_a, int32_t a_l2_norm, const float *table_b,
+                     void *ws_b, int64_t n_rel_b, int32_t b_l2_norm, const float *rel, int32_t rel_l2_norm, int64_t n_ent,
+                     int32_t rel_side, int32_t dim, int32_t ld, const int32_t *items, int64_t n, const float *rel_weight, float coef,
+                     double *loss_accum, void *stream);
 /* AttrE's character step (approaches/attre.py:88-109, 166-187; csrc/attre_step.hip), one wave per positive (e, a, v) and its
  * k = cfg->neg_group_k head-corrupted negatives (e', a, v), e' = neg_heads[p k .. p k + k):
  *   ue = l2n?(ent_ce)[e], wa = l2n?(attr)[a], v = sum_p w_p l2n?(chars)[value_chars[v, p]], w_p = sum_{m = p + 1 .. L} 1 / m,

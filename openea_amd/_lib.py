@@ -110,6 +110,12 @@ class ConvECfg(C.Structure):
     _fields_ = [("filter_num", C.c_int32), ("keep_prob", C.c_float), ("seed", C.c_uint64)]
 
 
+class MultiKENet(C.Structure):
+    """mirror of `oea_multike_net` (include/openea_hip.h)."""
+    _fields_ = [("p", C.c_void_p * 8), ("ent", C.c_void_p), ("step_workspace", C.c_void_p), ("n_rel_ws", C.c_int64),
+                ("weighted", C.c_int32), ("ent_l2_norm", C.c_int32), ("factor", C.c_float)]
+
+
 LOSS_KIND = {"margin-based": 0, "limited": 1, "logistic": 2, "positive": 3, "align": 4}
 OPT_KIND = {"SGD": 0, "Adagrad": 1, "Adam": 2, "Adadelta": 3}
 METRIC = {"inner": 0, "manhattan": 1, "euclidean": 2, "manhattan_f32": 3}
@@ -195,6 +201,12 @@ PROTOTYPES = {
     "oea_semantic_step": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, C.POINTER(StepCfg),
                                     _vp, _vp, _vp]),
     "oea_jape_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _f32, C.POINTER(StepCfg), _vp, _vp, _vp]),
+    "oea_multike_cnn_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "oea_multike_cnn_grads": (C.c_int, [_vp, _i32, _i32, _i64, _i32, C.POINTER(C.c_void_p)]),
+    "oea_multike_cnn_step": (C.c_int, [C.POINTER(MultiKENet), _i32, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _f32, _vp,
+                                       _i64, _vp, _i32, _vp]),
+    "oea_multike_rows": (C.c_int, [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp,
+                                   _f32, _vp, _vp]),
     "oea_attre_lds_chars": (_i64, [_i32]),
     "oea_attre_char_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "oea_attre_char_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64,

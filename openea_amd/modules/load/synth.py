@@ -145,6 +145,24 @@ def generate_attribute_triples(shape="EN-FR-15K-V1", seed=0, string_values=False
             _attribute_triples(rng, "kg2", profile, a2, t2, (seed, 2) if string_values else None))
 
 
+def literal_vectors(literals, dim, seed=0, literal_len=5):
+    """A stand-in for MultiKE's literal encoder (the reference encodes word vectors of a 1 M-word file with an auto-encoder):
+    the mean of per-word vectors, standard normal and seeded by (seed, crc32(word)), over the first literal_len words of a
+    literal; a literal without a word takes the empty word's vector -> float32 [len(literals), dim]."""
+    import zlib
+    cache = {}
+
+    def word(w):
+        if w not in cache:
+            cache[w] = np.random.RandomState([int(seed) & 0x7fffffff, zlib.crc32(w.encode('utf-8'))]).standard_normal(dim)
+        return cache[w]
+    out = np.zeros((len(literals), dim), np.float32)
+    for i, literal in enumerate(literals):
+        words = literal.split()[:literal_len] or ['']
+        out[i] = np.mean([word(w) for w in words], axis=0)
+    return out
+
+
 def make_kgs(shape="EN-FR-15K-V1", mode="mapping", ordered=True, seed=0, verbose=False, attributes=False, string_values=False):
     """-> KGs built through the same id-assignment code as a real dataset.  attributes=True adds generate_attribute_triples (for
     the shapes in ATTRIBUTES); the default has none, as before.  string_values=True (with attributes): string values."""

@@ -321,6 +321,80 @@ def jape_step(ent, ent_acc, rel, rel_acc, dim, pos, neg, neg_alpha, cfg, workspa
                               _stream()))
 
 
+# ---- MultiKE ----------------------------------------------------------------------------------------------------
+MULTIKE_MAX_DIM = 128
+MULTIKE_VARS = ("gamma", "beta", "K1", "b1", "K2", "b2", "W", "bd")
+MULTIKE_ROWS_CROSS, MULTIKE_ROWS_PULL, MULTIKE_ROWS_WSOFT = 0, 1, 2
+
+
+def multike_cnn_shapes(dim, ld=None):
+    """shapes of the eight variables of one parameter set, in the order of MULTIKE_VARS (W with row stride ld)"""
+    ld = pad4(dim) if ld is None else ld
+    return ((dim,), (dim,), (2, 4, 1, 2), (2,), (2, 4, 2, 2), (2,), (4 * dim, ld), (dim,))
+
+
+def multike_cnn_workspace(dim, ld, max_n, dev=None):
+    """workspace of multike_cnn_step for batches of up to max_n positives (no initialisation needed)"""
+    n = lib().oea_multike_cnn_workspace_bytes(int(dim), int(ld), int(max_n))
+    if n == 0:
+        raise OpenEAHipError("oea_multike_cnn_workspace_bytes: dim=%d ld=%d max_n=%d" % (dim, ld, max_n))
+    ws = torch.zeros(n, dtype=torch.uint8, device=dev or device())
+    ws._shape = (int(dim), int(ld), int(max_n))
+    return ws
+
+
+def multike_cnn_grads(workspace, net=0):
+    """views of the eight dense fp32 parameter gradients of net `net` that the last multike_cnn_step left in the workspace"""
+    dim, ld, max_n = workspace._shape
+    ptrs = (C.c_void_p * 8)()
+    check(lib().oea_multike_cnn_grads(_p(workspace), dim, ld, max_n, int(net), ptrs))
+    out = []
+    for ptr, shape in zip(ptrs, multike_cnn_shapes(dim, ld)):
+        off = ptr - workspace.data_ptr()
+        out.append(workspace[off:off + 4 * int(np.prod(shape))].view(torch.float32).view(shape))
+    return out
+
+
+def multike_net(params, ent, step_ws, n_rel_ws, weighted=False, ent_l2_norm=True, factor=1.0):
+    """one net of multike_cnn_step: its eight variables (MULTIKE_VARS), its entity table and that table's step workspace of
+    (ent rows, n_rel_ws) rows"""
+    assert len(params) == 8 and all(t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 for t in list(params) + [ent])
+    return dict(params=list(params), ent=ent, ws=step_ws, n_rel_ws=int(n_rel_ws), weighted=bool(weighted), l2n=bool(ent_l2_norm),
+                factor=float(factor))
+
+
+def multike_cnn_step(nets, attr, lit, dim, batch, attr_weight, lr, workspace, loss_accum, phase=PHASE_BOTH):
+    """The attribute CNN of MultiKE on batch int32 [n, 3] = (entity, attribute, literal) for 1 or 2 nets (multike_net) that share
+    attr [n_attr, ld] (raw) and lit [n_lit, ld] (constant); attr_weight float [n_attr] weights the positives of the weighted nets.
+    PHASE_GRAD: parameter gradients through multike_cnn_grads, row gradients in the nets' step workspaces (the attribute rows in
+    net 0's); PHASE_BOTH: SGD with lr on the parameters as well.  triple_step(..., empty, phase=PHASE_APPLY) on each table pair
+    finishes the step.  The loss of all nets is added to `loss_accum`."""
+    wdim, ld, max_n = workspace._shape
+    assert wdim == dim and attr.shape[1] == ld and lit.shape[1] == ld and batch.dtype == torch.int32 and batch.shape[1] == 3
+    arr = (_lib.MultiKENet * len(nets))()
+    for s, n in zip(arr, nets):
+        assert n["ent"].shape[1] == ld and n["params"][6].shape == (4 * dim, ld)
+        for i, t in enumerate(n["params"]):
+            s.p[i] = t.data_ptr()
+        s.ent, s.step_workspace, s.n_rel_ws = n["ent"].data_ptr(), n["ws"].data_ptr(), n["n_rel_ws"]
+        s.weighted, s.ent_l2_norm, s.factor = int(n["weighted"]), int(n["l2n"]), n["factor"]
+    check(lib().oea_multike_cnn_step(arr, len(nets), nets[0]["ent"].shape[0], _p(attr), attr.shape[0], _p(lit), lit.shape[0], dim, ld,
+                                     _p(batch), batch.shape[0], _p(attr_weight), float(lr), _p(workspace), max_n, _p(loss_accum),
+                                     int(phase), _stream()))
+
+
+def multike_rows(kind, table_a, ws_a, n_rel_a, table_b, ws_b, n_rel_b, rel, dim, items, coef, loss_accum, rel_weight=None,
+                 a_l2_norm=True, b_l2_norm=True, rel_l2_norm=True, rel_side=0):
+    """MultiKE's row-wise terms (oea_multike_rows): MULTIKE_ROWS_CROSS coef |A[h] + rel[r] - B[t]|^2, MULTIKE_ROWS_PULL
+    coef |A[e] - B[e]|^2 (ws_b None: B is constant), MULTIKE_ROWS_WSOFT coef rel_weight[r] softplus(|A[h] + rel[r] - B[t]|^2);
+    gradients into the step workspaces, the relation rows' into ws_a (rel_side 0) or ws_b (rel_side 1)."""
+    assert items.dtype == torch.int32
+    n = items.shape[0]
+    check(lib().oea_multike_rows(int(kind), _p(table_a), _p(ws_a), int(n_rel_a), int(bool(a_l2_norm)), _p(table_b), _p(ws_b),
+                                 int(n_rel_b), int(bool(b_l2_norm)), _p(rel), int(bool(rel_l2_norm)), table_a.shape[0], int(rel_side),
+                                 dim, table_a.shape[1], _p(items), n, _p(rel_weight), float(coef), _p(loss_accum), _stream()))
+
+
 # ---- AttrE ------------------------------------------------------------------------------------------------------
 ATTRE_MAX_DIM = 128
 ATTRE_MAX_LITERAL_LEN = 32

@@ -1,6 +1,6 @@
 """Hyper-parameter sets of the approaches on the hot path, as python dicts.
 
-The values are the ones the reference ships in run/args/{mtranse,bootea,aligne,gcnalign,transh,transd,hole,simple,rotate,iptranse,proje,conve,jape,imuse,attre,...}_args_{15K,100K}.json
+The values are the ones the reference ships in run/args/{mtranse,bootea,aligne,gcnalign,transh,transd,hole,simple,rotate,iptranse,proje,conve,jape,imuse,attre,multike,...}_args_{15K,100K}.json
 (the `args_*` API: one attribute per key).  ``get_args(name, scale)`` returns an ``ARGs`` object that any
 model accepts through ``set_args``; a reference JSON file loaded with ``load_args`` works the same way.
 """
@@ -86,6 +86,16 @@ _ARGS = {
                   attr_l2_norm=True, char_l2_norm=True, loss_norm="L2", margin=1.5, loss="margin-based", neg_sampling="uniform",
                   neg_triple_num=1, learning_rate=0.01, optimizer="SGD", batch_size=5000, eval_metric="inner", eval_norm=True,
                   literal_len=5),
+    # run/args/multike_args_15K.json (literal_vectors_path is ours: approaches/multi_ke.py reads it in place of word2vec_path)
+    "MultiKE": dict(embedding_module="MultiKE", alignment_module="swapping", word2vec_path="../../datasets/wiki-news-300d-1M.vec",
+                    word2vec_dim=300, literal_vectors_path=None, dim=100, init="xavier", ent_l2_norm=True, rel_l2_norm=True,
+                    attr_l2_norm=True, loss_norm="L2", margin=1.5, loss="margin-based", encoder_epoch=100, encoder_active="thah",
+                    encoder_normalize=True, retrain_literal_embeds=True, literal_normalize=True, literal_len=5, neg_triple_num=10,
+                    neg_sampling="normal", truncated_epsilon=0.98, truncated_freq=20, learning_rate=0.001, optimizer="SGD",
+                    shared_learning_max_epoch=200, batch_size=5000, entity_batch_size=5000, attribute_batch_size=5000,
+                    start_valid=10, eval_metric="inner", eval_norm=True, orthogonal_weight=2, cv_name_weight=1, cv_weight=1,
+                    start_predicate_soft_alignment=10, predicate_soft_sim=0.80, predicate_init_sim=0.90,
+                    relation_learning_rate=0.005, ITC_learning_rate=0.004),
     "GCN_Align": dict(embedding_module="GCN_Align", alignment_module="mapping", dim=100, neg_sampling="uniform",
                       neg_triple_num=5, learning_rate=8, batch_size=5000, test_threads_num=3, eval_metric="manhattan",
                       eval_norm=False, support_number=1, se_dim=100, ae_dim=100, hidden1=100, gamma=3,
@@ -121,6 +131,7 @@ _SCALE_100K = {
     "JAPE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
     "IMUSE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10, start_valid=100),
     "AttrE": dict(batch_size=20000, batch_threads_num=3, test_threads_num=10),
+    "MultiKE": dict(batch_size=20000, batch_threads_num=4, test_threads_num=10),
     "GCN_Align": dict(batch_size=20000, learning_rate=25),
     "AliNet": dict(batch_size=20000, truncated_epsilon=0.995, min_rel_win=15),
     "RDGCN": dict(batch_size=20000, learning_rate=0.001, start_valid=50),
