@@ -91,9 +91,7 @@ static size_t ws_layout(int64_t n_ent, int64_t n_rel, int32_t ld, void *base, St
 
 // ---- lane-strided row fragments ------------------------------------------------------------------
 template <int G, int IT>
-struct Row {
-    float v[IT];
-};
+struct Row;                 // (below its loaders)
 
 // TIGHT (G == 32 only): the dispatch gives ld > (IT - 1) * 32, so only the last fragment needs the bound.  Used by the
 // grouped scoring kernel (18.8 vs 19.2 us at the 15K shape, 64 vs 75 us at the 100K shape); apply_rows is SLOWER with it
@@ -123,6 +121,43 @@ __device__ __forceinline__ void load_grad_row(const grad_t *__restrict__ base, i
         r.v[it] = c < ld ? oea::grad_val(base[c]) : 0.f;
     }
 }
+// Lane l of a G-lane group holds elements l, l + G, ... of a row: IT fragments of one scalar.  The members are what the optimiser
+// asks of a row; Row4 (with apply_one_row) answers the same calls on float4 fragments.  s(it, j): scalar j of fragment it, whose
+// first column is col(it, lane).  dot_partial adds its products in ascending order and the signed forms take the sign as a select:
+// the order and the form that this layout's bits rest on.
+template <int G, int IT>
+struct Row {
+    static constexpr int kLanes = G, kFrags = IT, kWidth = 1;
+    float v[IT];
+    __device__ __forceinline__ static int col(int it, int lane) { return it * G + lane; }
+    __device__ __forceinline__ float s(int it, int) const { return v[it]; }
+    __device__ __forceinline__ static void put(float *p, const float (&x)[1]) { *p = x[0]; }
+    __device__ __forceinline__ static void zero(grad_t *p) { *p = 0; }
+    __device__ __forceinline__ void load(const float *__restrict__ base, int ld, int lane) { load_row<G, IT>(base, ld, lane, *this); }
+    __device__ __forceinline__ void load_grad(const grad_t *__restrict__ base, int ld, int lane) { load_grad_row<G, IT>(base, ld, lane, *this); }
+    __device__ __forceinline__ float dot_partial(const Row &o) const {
+        float p = 0.f;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) p += v[it] * o.v[it];
+        return p;
+    }
+    __device__ __forceinline__ void set_signed(const Row &o, bool neg) {
+#pragma unroll
+        for (int it = 0; it < IT; ++it) v[it] = neg ? -o.v[it] : o.v[it];
+    }
+    __device__ __forceinline__ void add_signed(const Row &o, bool neg) {
+#pragma unroll
+        for (int it = 0; it < IT; ++it) v[it] += neg ? -o.v[it] : o.v[it];
+    }
+    // += o, and the scratch row g it was loaded from cleared on the way
+    __device__ __forceinline__ void add_and_clear(const Row &o, grad_t *g, int ld, int lane) {
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            v[it] += o.v[it];
+            if (col(it, lane) < ld) zero(g + col(it, lane));
+        }
+    }
+};
 template <int G, int IT>
 __device__ __forceinline__ float sumsq(const Row<G, IT> &r) {
     float s = 0.f;
@@ -1268,36 +1303,96 @@ __global__ __launch_bounds__(256) void apply_normal_rows(int64_t n_rel, int ld, 
 }
 
 // ---- kernel 2: optimiser on touched rows (relation rows first, then entity rows) -------------------
-// pull the summed gradient of one row back through the normalisation, apply Adagrad / SGD, clear the scratch row
-// CLEAR = false: the gradient did not come from the scratch row (apply_rows_plan): nothing to zero
-template <int G, int IT, bool CLEAR = true>
+// Row's interface on float4 fragments (the fp32 scratch; ld % 4 == 0: a float4 is inside the row or past it).  A group of G lanes
+// holds IT4 = ceil(ld / (4 G)) float4 per row (ld = 100, G = 16: two loads per row instead of seven dwords), a quarter of the memory
+// instructions per row stream: the planned optimiser is ONE residency of latency-bound chains (record -> rows -> stores), so what
+// it issues per row is what it costs.  dot_partial adds ((x x + y y) + z z) + w w per fragment to the running sum and add_signed is
+// an fma by +-1 (exact): this layout's order and form, which fix its bits.
+template <int G, int IT4>
+struct Row4 {
+    static constexpr int kLanes = G, kFrags = IT4, kWidth = 4;
+    float v[IT4][4];
+    __device__ __forceinline__ static int col(int it, int lane) { return (it * G + lane) * 4; }
+    __device__ __forceinline__ float s(int it, int j) const { return v[it][j]; }
+    __device__ __forceinline__ static void put(float *p, const float (&x)[4]) { oea::st4(p, make_float4(x[0], x[1], x[2], x[3])); }
+    __device__ __forceinline__ static void zero(float *p) { oea::st4(p, make_float4(0.f, 0.f, 0.f, 0.f)); }
+    __device__ __forceinline__ void load(const float *__restrict__ base, int ld, int lane) {
+#pragma unroll
+        for (int it = 0; it < IT4; ++it) {
+            const int c = col(it, lane);
+            const float4 f = c < ld ? oea::ld4(base + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[it][0] = f.x; v[it][1] = f.y; v[it][2] = f.z; v[it][3] = f.w;
+        }
+    }
+    __device__ __forceinline__ void load_grad(const float *__restrict__ base, int ld, int lane) { load(base, ld, lane); }
+    __device__ __forceinline__ float dot_partial(const Row4 &o) const {
+        float p = 0.f;
+#pragma unroll
+        for (int it = 0; it < IT4; ++it) p += v[it][0] * o.v[it][0] + v[it][1] * o.v[it][1] + v[it][2] * o.v[it][2] + v[it][3] * o.v[it][3];
+        return p;
+    }
+    __device__ __forceinline__ void set_signed(const Row4 &o, bool neg) {
+        const float sg = neg ? -1.f : 1.f;
+#pragma unroll
+        for (int it = 0; it < IT4; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[it][j] = sg * o.v[it][j];
+    }
+    __device__ __forceinline__ void add_signed(const Row4 &o, bool neg) {
+        const float sg = neg ? -1.f : 1.f;
+#pragma unroll
+        for (int it = 0; it < IT4; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[it][j] = fmaf(sg, o.v[it][j], v[it][j]);
+    }
+    __device__ __forceinline__ void add_and_clear(const Row4 &o, float *g, int ld, int lane) {
+#pragma unroll
+        for (int it = 0; it < IT4; ++it) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[it][j] += o.v[it][j];
+            if (col(it, lane) < ld) zero(g + col(it, lane));
+        }
+    }
+};
+
+// pull the summed gradient of one row back through the normalisation, apply Adagrad / SGD, clear the scratch row.  F: Row or Row4.
+// CLEAR = false: the gradient did not come from the scratch row (the planned optimiser's gathered sums): nothing to zero
+template <bool CLEAR = true, class F>
 __device__ __forceinline__ void apply_one_row(float *__restrict__ v, float *__restrict__ acc, grad_t *__restrict__ g,
                                               flag_t *__restrict__ touched_flag, int ld, int lane, int on,
-                                              const oea_step_cfg &cfg, const Row<G, IT> &rv, Row<G, IT> &rg,
-                                              const Row<G, IT> &ra) {
+                                              const oea_step_cfg &cfg, const F &rv, const F &rg, const F &ra) {
     float inv = 1.f, ydg = 0.f;
     if (on) {
-        const float ss = sumsq<G, IT>(rv);
+        const float ss = group_sum<F::kLanes>(rv.dot_partial(rv));
         inv = rsqrtf(fmaxf(ss, 1e-12f));
-        float dot = 0.f;
-#pragma unroll
-        for (int it = 0; it < IT; ++it) dot += rv.v[it] * rg.v[it];
-        dot = group_sum<G>(dot) * inv;           // y . g
+        const float dot = group_sum<F::kLanes>(rv.dot_partial(rg)) * inv;       // y . g
         ydg = ss > 1e-12f ? dot : 0.f;
     }
 #pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        const int c = it * G + lane;
+    for (int it = 0; it < F::kFrags; ++it) {
+        const int c = F::col(it, lane);
         if (c < ld) {
-            const float gv = on ? (rg.v[it] - rv.v[it] * inv * ydg) * inv : rg.v[it];
-            if (cfg.opt_kind == OEA_OPT_ADAGRAD) {
-                const float a = ra.v[it] + gv * gv;
-                acc[c] = a;
-                v[c] = rv.v[it] - cfg.lr * gv / sqrtf(a);
-            } else {
-                v[c] = rv.v[it] - cfg.lr * gv;
+            float gv[F::kWidth], nv[F::kWidth];
+#pragma unroll
+            for (int j = 0; j < F::kWidth; ++j) gv[j] = rg.s(it, j);
+            if (on) {
+#pragma unroll
+                for (int j = 0; j < F::kWidth; ++j) gv[j] = (gv[j] - rv.s(it, j) * inv * ydg) * inv;
             }
-            if (CLEAR) g[c] = 0;
+            if (cfg.opt_kind == OEA_OPT_ADAGRAD) {
+                float a[F::kWidth];
+#pragma unroll
+                for (int j = 0; j < F::kWidth; ++j) a[j] = ra.s(it, j) + gv[j] * gv[j];
+                F::put(acc + c, a);
+#pragma unroll
+                for (int j = 0; j < F::kWidth; ++j) nv[j] = rv.s(it, j) - cfg.lr * gv[j] / sqrtf(a[j]);
+                F::put(v + c, nv);
+            } else {
+#pragma unroll
+                for (int j = 0; j < F::kWidth; ++j) nv[j] = rv.s(it, j) - cfg.lr * gv[j];
+                F::put(v + c, nv);
+            }
+            if (CLEAR) F::zero(g + c);
         }
     }
     if (CLEAR && lane == 0) *touched_flag = 0;
@@ -1347,7 +1442,33 @@ __device__ __forceinline__ void apply_relation_row(int64_t row, float *__restric
     }
 #pragma unroll
     for (int it = 0; it < IT; ++it) rg.v[it] = oea::grad_val(q[it]);
-    apply_one_row<G, IT>(v, acc, g, ws.rel_touched + row, ld, lane, cfg.rel_l2_norm, cfg, rv, rg, ra);
+    apply_one_row(v, acc, g, ws.rel_touched + row, ld, lane, cfg.rel_l2_norm, cfg, rv, rg, ra);
+}
+
+// The loss partials of the scoring kernel into *loss_accum, in a fixed order.  By one wave (threads 0..63 of a block call it) ...
+__device__ __forceinline__ void add_loss_partials_wave(const StepWs &ws, int n_partials, double *__restrict__ loss_accum) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_partials; i += 64) s += ws.partials[i];
+    s = oea::wave_sum_d(s);
+    if (threadIdx.x == 0) *loss_accum += s;
+}
+// ... or by a whole block of 256: every lane a strided share (all loads in flight), then a fixed tree
+__device__ __forceinline__ void add_loss_partials_block(const StepWs &ws, int n_partials, double *__restrict__ loss_accum) {
+    static_assert(kMaxBlocks <= 16 * 256, "the block reads 16 partials per lane");
+    __shared__ double sp[256];
+    double v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { const int i = u * 256 + (int)threadIdx.x; v[u] = i < n_partials ? ws.partials[i] : 0.0; }
+    double acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc += v[u];
+    sp[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sp[threadIdx.x] += sp[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss_accum += sp[0];
 }
 
 // Work item w of the grid: w < n_rel -> relation row w (sums its 16 scratch copies); else R consecutive entity rows.
@@ -1386,20 +1507,14 @@ __global__ __launch_bounds__(256) void apply_rows(float *__restrict__ ent, float
             for (int r = 0; r < R; ++r) {
                 if (flag[r] == 0.f) continue;
                 const int64_t row = row0 + r;
-                apply_one_row<G, IT>(ent + row * ld, ent_acc + row * ld, ws.ent_grad + row * ld, ws.ent_touched + row, ld,
+                apply_one_row(ent + row * ld, ent_acc + row * ld, ws.ent_grad + row * ld, ws.ent_touched + row, ld,
                                      lane, cfg.ent_l2_norm, cfg, rv[r], rg[r], ra[r]);
             }
             continue;
         }
         apply_relation_row<G, IT>(w, rel, rel_acc, ld, lane, cfg, ws, copies_folded);
     }
-    // fixed-order reduction of the loss partials by one wave of block 0
-    if (blockIdx.x == 0 && threadIdx.x < 64) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < n_partials; i += 64) s += ws.partials[i];
-        s = oea::wave_sum_d(s);
-        if (threadIdx.x == 0) *loss_accum += s;
-    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) add_loss_partials_wave(ws, n_partials, loss_accum);
 }
 
 // ---- kernel 2', round 6: the optimiser of a PLANNED step (step_plan.h), one launch, four kinds of blocks ----------------------------------
@@ -1415,7 +1530,8 @@ __global__ __launch_bounds__(256) void apply_rows(float *__restrict__ ent, float
 //                          wave would work through them alone.  Rows the plan sums are left to their group (membership map);
 //   last block             the loss partials, 256 lanes + a fixed tree (one wave walking 2,500 partials took 18 us).
 // Same update everywhere: gradient back through the normalisation, Adagrad / SGD (apply_one_row).
-template <int G, int IT>
+// V4: the entity rows (plan rows and flag-scan rows) travel as float4 (Row4) instead of dwords (Row); relation rows are dwords either way.
+template <int G, int IT, bool V4>
 __global__ __launch_bounds__(256) void apply_step_plan(float *__restrict__ ent, float *__restrict__ ent_acc, int64_t n_ent,
                                                        float *__restrict__ rel, float *__restrict__ rel_acc, int64_t n_rel, int ld,
                                                        oea_step_cfg cfg, StepWs ws, int n_partials, double *__restrict__ loss_accum,
@@ -1423,6 +1539,7 @@ __global__ __launch_bounds__(256) void apply_step_plan(float *__restrict__ ent, 
                                                        const uint4 *__restrict__ recs, const uint32_t *__restrict__ vals,
                                                        const int32_t *__restrict__ step_first, int s, const uint8_t *__restrict__ inplan,
                                                        const float *__restrict__ contrib) {
+    using F = std::conditional_t<V4, Row4<G, (IT + 3) / 4>, Row<G, IT>>;
     constexpr int GPB = 256 / G, GPW = 64 / G;
     const int lane = threadIdx.x % G;
     const int b = (int)blockIdx.x, nb = (int)gridDim.x;
@@ -1439,39 +1556,30 @@ __global__ __launch_bounds__(256) void apply_step_plan(float *__restrict__ ent, 
             const int64_t row = rec.x;
             const uint32_t e0 = rec.y, e1 = rec.y + rec.z, v0 = rec.w;
             const float flag = (float)ws.ent_touched[row];
-            Row<G, IT> rv, ra, rg, rc;
-            load_row<G, IT>(ent + row * ld, ld, lane, rv);
-            if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row<G, IT>(ent_acc + row * ld, ld, lane, ra);
-            load_row<G, IT>(contrib + (int64_t)(v0 & 0x7fffffffu) * ld, ld, lane, rc);
-#pragma unroll
-            for (int it = 0; it < IT; ++it) rg.v[it] = (v0 >> 31) ? -rc.v[it] : rc.v[it];
+            F rv, ra, rg, rc;
+            rv.load(ent + row * ld, ld, lane);
+            if (cfg.opt_kind == OEA_OPT_ADAGRAD) ra.load(ent_acc + row * ld, ld, lane);
+            rc.load(contrib + (int64_t)(v0 & 0x7fffffffu) * ld, ld, lane);
+            rg.set_signed(rc, v0 >> 31);
             for (uint32_t e = e0 + 1; e < e1; e += 3) {                // further references to the row, in batch order, three in flight
                 uint32_t ve[3];
-                Row<G, IT> r3[3];
+                F r3[3];
 #pragma unroll
                 for (int u = 0; u < 3; ++u) ve[u] = vals[min(e + u, e1 - 1)];
 #pragma unroll
-                for (int u = 0; u < 3; ++u) load_row<G, IT>(contrib + (int64_t)(ve[u] & 0x7fffffffu) * ld, ld, lane, r3[u]);
+                for (int u = 0; u < 3; ++u) r3[u].load(contrib + (int64_t)(ve[u] & 0x7fffffffu) * ld, ld, lane);
 #pragma unroll
                 for (int u = 0; u < 3; ++u)
-                    if (e + u < e1) {
-#pragma unroll
-                        for (int it = 0; it < IT; ++it) rg.v[it] += (ve[u] >> 31) ? -r3[u].v[it] : r3[u].v[it];
-                    }
+                    if (e + u < e1) rg.add_signed(r3[u], ve[u] >> 31);
             }
             if (flag != 0.f) {                                         // + what the atomic scratch holds for this row
                 grad_t *g = ws.ent_grad + row * ld;
-                Row<G, IT> rs;
-                load_grad_row<G, IT>(g, ld, lane, rs);
-#pragma unroll
-                for (int it = 0; it < IT; ++it) {
-                    rg.v[it] += rs.v[it];
-                    const int c = it * G + lane;
-                    if (c < ld) g[c] = 0;
-                }
+                F rs;
+                rs.load_grad(g, ld, lane);
+                rg.add_and_clear(rs, g, ld, lane);
                 if (lane == 0) ws.ent_touched[row] = 0;
             }
-            apply_one_row<G, IT, false>(ent + row * ld, ent_acc + row * ld, nullptr, nullptr, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
+            apply_one_row<false>(ent + row * ld, ent_acc + row * ld, nullptr, nullptr, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
         }
     } else if (b < nb - 1) {
         // (the scan's blocks come BEFORE the plan's in the grid: its waves work through their flagged rows one group-load at a time --
@@ -1495,204 +1603,19 @@ __global__ __launch_bounds__(256) void apply_step_plan(float *__restrict__ ent, 
                         if (gw == q) row = (int64_t)bit * n_chunk + chunk;
                     }
                 if (row >= 0) {
-                    Row<G, IT> rv, rg, ra;
-                    load_row<G, IT>(ent + row * ld, ld, lane, rv);
-                    load_grad_row<G, IT>(ws.ent_grad + row * ld, ld, lane, rg);
-                    if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row<G, IT>(ent_acc + row * ld, ld, lane, ra);
-                    apply_one_row<G, IT>(ent + row * ld, ent_acc + row * ld, ws.ent_grad + row * ld, ws.ent_touched + row, ld, lane,
-                                         cfg.ent_l2_norm, cfg, rv, rg, ra);
+                    F rv, rg, ra;
+                    rv.load(ent + row * ld, ld, lane);
+                    rg.load_grad(ws.ent_grad + row * ld, ld, lane);
+                    if (cfg.opt_kind == OEA_OPT_ADAGRAD) ra.load(ent_acc + row * ld, ld, lane);
+                    apply_one_row(ent + row * ld, ent_acc + row * ld, ws.ent_grad + row * ld, ws.ent_touched + row, ld, lane,
+                                  cfg.ent_l2_norm, cfg, rv, rg, ra);
                 }
             }
         }
     } else {
-        // the loss partials of the scoring kernel: every lane a strided share (all loads in flight), then a fixed tree
-        __shared__ double sp[256];
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) { const int i = u * 256 + (int)threadIdx.x; v[u] = i < n_partials ? ws.partials[i] : 0.0; }
-        double acc = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc += v[u];
-        sp[threadIdx.x] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sp[threadIdx.x] += sp[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *loss_accum += sp[0];
+        add_loss_partials_block(ws, n_partials, loss_accum);
     }
 }
-
-#ifndef OEA_DET_SCRATCH
-// ---- apply_step_plan with rows as float4 (round 6) ------------------------------------------------------------------------------------------
-// The same launch and the same four kinds of blocks; the entity rows (plan rows and flag-scan rows) travel as 16 B per lane: a lane
-// group of G lanes holds IT4 = ceil(ld / (4 G)) float4 per row (ld = 100, G = 16: two loads per row instead of seven dwords), a quarter
-// of the memory instructions and of the registers per row stream -- the kernel is ONE residency of latency-bound chains
-// (record -> rows -> stores), so what it issues per row is what it costs.  Relation rows and loss partials as in apply_step_plan.
-template <int IT4>
-struct Row4 {
-    float4 v[IT4];
-};
-template <int G, int IT4>
-__device__ __forceinline__ void load_row4(const float *__restrict__ base, int ld, int lane, Row4<IT4> &r) {
-#pragma unroll
-    for (int it = 0; it < IT4; ++it) {
-        const int c = (it * G + lane) * 4;                          // ld % 4 == 0: a float4 is inside the row or past it
-        r.v[it] = c < ld ? oea::ld4(base + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-__device__ __forceinline__ float4 f4_axpy(float a, float4 x, float4 y) { return make_float4(fmaf(a, x.x, y.x), fmaf(a, x.y, y.y), fmaf(a, x.z, y.z), fmaf(a, x.w, y.w)); }
-__device__ __forceinline__ float4 f4_add(float4 x, float4 y) { return make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w); }
-__device__ __forceinline__ float f4_dot(float4 x, float4 y) { return x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w; }
-
-// apply_one_row on float4 fragments (fp32 scratch): back through the normalisation, Adagrad / SGD, optional clear of the scratch row
-template <int G, int IT4, bool CLEAR>
-__device__ __forceinline__ void apply_one_row4(float *__restrict__ v, float *__restrict__ acc, float *__restrict__ g, flag_t *__restrict__ touched_flag,
-                                               int ld, int lane, int on, const oea_step_cfg &cfg, const Row4<IT4> &rv, const Row4<IT4> &rg,
-                                               const Row4<IT4> &ra) {
-    float inv = 1.f, ydg = 0.f;
-    if (on) {
-        float ss = 0.f, dot = 0.f;
-#pragma unroll
-        for (int it = 0; it < IT4; ++it) { ss += f4_dot(rv.v[it], rv.v[it]); dot += f4_dot(rv.v[it], rg.v[it]); }
-        ss = group_sum<G>(ss);
-        inv = rsqrtf(fmaxf(ss, 1e-12f));
-        dot = group_sum<G>(dot) * inv;
-        ydg = ss > 1e-12f ? dot : 0.f;
-    }
-#pragma unroll
-    for (int it = 0; it < IT4; ++it) {
-        const int c = (it * G + lane) * 4;
-        if (c < ld) {
-            float4 gv = rg.v[it];
-            const float4 y = rv.v[it];
-            if (on)                                                  // (g - y (y . g)) / |v|, y = v / |v|: apply_one_row's expression
-                gv = make_float4((gv.x - y.x * inv * ydg) * inv, (gv.y - y.y * inv * ydg) * inv, (gv.z - y.z * inv * ydg) * inv,
-                                 (gv.w - y.w * inv * ydg) * inv);
-            float4 nv;
-            if (cfg.opt_kind == OEA_OPT_ADAGRAD) {
-                const float4 a = make_float4(ra.v[it].x + gv.x * gv.x, ra.v[it].y + gv.y * gv.y, ra.v[it].z + gv.z * gv.z,
-                                             ra.v[it].w + gv.w * gv.w);
-                oea::st4(acc + c, a);
-                nv = make_float4(rv.v[it].x - cfg.lr * gv.x / sqrtf(a.x), rv.v[it].y - cfg.lr * gv.y / sqrtf(a.y),
-                                 rv.v[it].z - cfg.lr * gv.z / sqrtf(a.z), rv.v[it].w - cfg.lr * gv.w / sqrtf(a.w));
-            } else {
-                nv = make_float4(y.x - cfg.lr * gv.x, y.y - cfg.lr * gv.y, y.z - cfg.lr * gv.z, y.w - cfg.lr * gv.w);
-            }
-            oea::st4(v + c, nv);
-            if (CLEAR) oea::st4(g + c, make_float4(0.f, 0.f, 0.f, 0.f));
-        }
-    }
-    if (CLEAR && lane == 0) *touched_flag = 0;
-}
-
-template <int G, int IT>
-__global__ __launch_bounds__(256) void apply_step_plan_v4(float *__restrict__ ent, float *__restrict__ ent_acc, int64_t n_ent,
-                                                          float *__restrict__ rel, float *__restrict__ rel_acc, int64_t n_rel, int ld,
-                                                          oea_step_cfg cfg, StepWs ws, int n_partials, double *__restrict__ loss_accum,
-                                                          int copies_folded, int rel_blocks, int scan_blocks,
-                                                          const uint4 *__restrict__ recs, const uint32_t *__restrict__ vals,
-                                                          const int32_t *__restrict__ step_first, int s, const uint8_t *__restrict__ inplan,
-                                                          const float *__restrict__ contrib) {
-    constexpr int GPB = 256 / G, GPW = 64 / G, IT4 = (IT + 3) / 4;
-    const int lane = threadIdx.x % G;
-    const int b = (int)blockIdx.x, nb = (int)gridDim.x;
-    if (b < rel_blocks) {
-        for (int64_t row = (int64_t)b * GPB + threadIdx.x / G; row < n_rel; row += (int64_t)rel_blocks * GPB)
-            apply_relation_row<G, IT>(row, rel, rel_acc, ld, lane, cfg, ws, copies_folded);
-    } else if (b >= rel_blocks + scan_blocks && b < nb - 1) {
-        const int plan_blocks = nb - 1 - rel_blocks - scan_blocks;
-        const int64_t grp = (int64_t)(b - rel_blocks - scan_blocks) * GPB + threadIdx.x / G, ngrp = (int64_t)plan_blocks * GPB;
-        const int64_t i1 = step_first[s + 1];
-        for (int64_t i = step_first[s] + grp; i < i1; i += ngrp) {
-            const uint4 rec = recs[i];                                 // {row, first entry, entries, first entry's value}
-            if (rec.z > oea::kPlanHubEntries) continue;
-            const int64_t row = rec.x;
-            const uint32_t e0 = rec.y, e1 = rec.y + rec.z, v0 = rec.w;
-            const float flag = (float)ws.ent_touched[row];
-            Row4<IT4> rv, ra, rg, rc;
-            load_row4<G, IT4>(ent + row * ld, ld, lane, rv);
-            if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row4<G, IT4>(ent_acc + row * ld, ld, lane, ra);
-            load_row4<G, IT4>(contrib + (int64_t)(v0 & 0x7fffffffu) * ld, ld, lane, rc);
-            const float s0 = (v0 >> 31) ? -1.f : 1.f;
-#pragma unroll
-            for (int it = 0; it < IT4; ++it) rg.v[it] = make_float4(s0 * rc.v[it].x, s0 * rc.v[it].y, s0 * rc.v[it].z, s0 * rc.v[it].w);
-            for (uint32_t e = e0 + 1; e < e1; e += 3) {                // further references to the row, in batch order, three in flight
-                uint32_t ve[3];
-                Row4<IT4> r3[3];
-#pragma unroll
-                for (int u = 0; u < 3; ++u) ve[u] = vals[min(e + u, e1 - 1)];
-#pragma unroll
-                for (int u = 0; u < 3; ++u) load_row4<G, IT4>(contrib + (int64_t)(ve[u] & 0x7fffffffu) * ld, ld, lane, r3[u]);
-#pragma unroll
-                for (int u = 0; u < 3; ++u)
-                    if (e + u < e1) {
-                        const float su = (ve[u] >> 31) ? -1.f : 1.f;
-#pragma unroll
-                        for (int it = 0; it < IT4; ++it) rg.v[it] = f4_axpy(su, r3[u].v[it], rg.v[it]);
-                    }
-            }
-            if (flag != 0.f) {                                         // + what the atomic scratch holds for this row
-                float *g = ws.ent_grad + row * ld;
-                Row4<IT4> rs;
-                load_row4<G, IT4>(g, ld, lane, rs);
-#pragma unroll
-                for (int it = 0; it < IT4; ++it) {
-                    rg.v[it] = f4_add(rg.v[it], rs.v[it]);
-                    const int c = (it * G + lane) * 4;
-                    if (c < ld) oea::st4(g + c, make_float4(0.f, 0.f, 0.f, 0.f));
-                }
-                if (lane == 0) ws.ent_touched[row] = 0;
-            }
-            apply_one_row4<G, IT4, false>(ent + row * ld, ent_acc + row * ld, nullptr, nullptr, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
-        }
-    } else if (b < nb - 1) {
-        const int first = rel_blocks;
-        const int wl = threadIdx.x & 63, gw = wl / G;
-        const int64_t wave = (int64_t)(b - first) * 4 + (threadIdx.x >> 6), nwave = (int64_t)scan_blocks * 4;
-        const int64_t n_chunk = (n_ent + 63) / 64;
-        const uint8_t *mine = inplan + (int64_t)s * n_ent;
-        for (int64_t chunk = wave; chunk < n_chunk; chunk += nwave) {
-            const int64_t r = (int64_t)wl * n_chunk + chunk;
-            const bool todo = r < n_ent && (float)ws.ent_touched[r] != 0.f && mine[r] == 0;
-            unsigned long long mask = __ballot(todo);
-            while (mask) {
-                int64_t row = -1;
-#pragma unroll
-                for (int q = 0; q < GPW; ++q)
-                    if (mask) {
-                        const int bit = __builtin_ctzll(mask);
-                        mask &= mask - 1;
-                        if (gw == q) row = (int64_t)bit * n_chunk + chunk;
-                    }
-                if (row >= 0) {
-                    Row4<IT4> rv, rg, ra;
-                    load_row4<G, IT4>(ent + row * ld, ld, lane, rv);
-                    load_row4<G, IT4>(ws.ent_grad + row * ld, ld, lane, rg);
-                    if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row4<G, IT4>(ent_acc + row * ld, ld, lane, ra);
-                    apply_one_row4<G, IT4, true>(ent + row * ld, ent_acc + row * ld, ws.ent_grad + row * ld, ws.ent_touched + row, ld, lane,
-                                                 cfg.ent_l2_norm, cfg, rv, rg, ra);
-                }
-            }
-        }
-    } else {
-        __shared__ double sp[256];
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) { const int i = u * 256 + (int)threadIdx.x; v[u] = i < n_partials ? ws.partials[i] : 0.0; }
-        double acc = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc += v[u];
-        sp[threadIdx.x] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sp[threadIdx.x] += sp[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) *loss_accum += sp[0];
-    }
-}
-#endif  // !OEA_DET_SCRATCH
 
 // ---- kernel 2b: optimisers whose update is DENSE (tf.train.AdamOptimizer / AdadeltaOptimizer, optimizers.py:13-16) -------
 // The tables are l2_normalize(variable): the gradient of a gather comes back through the normalisation as a dense
@@ -1760,12 +1683,7 @@ __global__ __launch_bounds__(256) void apply_rows_dense(float *__restrict__ ent,
         }
         if (flag != 0.f && lane == 0) touched[row] = 0;
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < n_partials; i += 64) s += ws.partials[i];
-        s = oea::wave_sum_d(s);
-        if (threadIdx.x == 0) *loss_accum += s;
-    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) add_loss_partials_wave(ws, n_partials, loss_accum);
 }
 
 // ---- entity-id partitioning of the step (one process per GPU; BASELINE.json north_star) -----------------------
@@ -1824,6 +1742,21 @@ __global__ __launch_bounds__(256) void part_pack_kernel(StepWs ws, int64_t n_ent
     }
 }
 
+// one relation row of the partitioned jobs: its gradient is the row of rel_x (summed over the ranks), its flag follows rel_x's rows
+// (rv, rg, ra: the caller's fragments, which its entity rows use next.  With fragments of its own the kernels take more registers:
+//  part_apply_kernel<64, 8> 62 -> 69 VGPRs, 8 -> 7 waves per SIMD)
+template <int G, int IT>
+__device__ __forceinline__ void apply_exchanged_relation_row(int64_t r, float *rel, float *rel_acc, int64_t n_rel, int ld, int lane,
+                                                             grad_t *rel_x, const oea_step_cfg &cfg, Row<G, IT> &rv, Row<G, IT> &rg,
+                                                             Row<G, IT> &ra) {
+    if (rel_x[n_rel * ld + r] == 0) return;
+    rv.load(rel + r * ld, ld, lane);
+    rg.load_grad(rel_x + r * ld, ld, lane);
+    if (cfg.opt_kind == OEA_OPT_ADAGRAD) ra.load(rel_acc + r * ld, ld, lane);
+    flag_t dummy;
+    apply_one_row(rel + r * ld, rel_acc + r * ld, rel_x + r * ld, &dummy, ld, lane, cfg.rel_l2_norm, cfg, rv, rg, ra);
+}
+
 template <int G, int IT>
 __global__ __launch_bounds__(256) void part_apply_kernel(float *__restrict__ ent, float *__restrict__ acc_own, int64_t n_ent,
                                                          float *__restrict__ rel, float *__restrict__ rel_acc, int64_t n_rel,
@@ -1836,13 +1769,7 @@ __global__ __launch_bounds__(256) void part_apply_kernel(float *__restrict__ ent
     for (int64_t w = grp; w < rpr + n_rel; w += ngrp) {
         Row<G, IT> rv, rg, ra;
         if (w >= rpr) {
-            const int64_t r = w - rpr;
-            if (rel_x[n_rel * ld + r] == 0) continue;
-            load_row<G, IT>(rel + r * ld, ld, lane, rv);
-            load_grad_row<G, IT>(rel_x + r * ld, ld, lane, rg);
-            if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row<G, IT>(rel_acc + r * ld, ld, lane, ra);
-            flag_t dummy;
-            apply_one_row<G, IT>(rel + r * ld, rel_acc + r * ld, rel_x + r * ld, &dummy, ld, lane, cfg.rel_l2_norm, cfg, rv, rg, ra);
+            apply_exchanged_relation_row<G, IT>(w - rpr, rel, rel_acc, n_rel, ld, lane, rel_x, cfg, rv, rg, ra);
             continue;
         }
         const int64_t j = w, id = j * world + rank;
@@ -1857,18 +1784,13 @@ __global__ __launch_bounds__(256) void part_apply_kernel(float *__restrict__ ent
             load_grad_row<G, IT>(own + j * ld, ld, lane, rg);
             if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row<G, IT>(acc_own + j * ld, ld, lane, ra);
             flag_t dummy;
-            apply_one_row<G, IT>(v, acc_own + j * ld, own + j * ld, &dummy, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
+            apply_one_row(v, acc_own + j * ld, own + j * ld, &dummy, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
             load_row<G, IT>(v, ld, lane, rv);                      // the updated row (same lanes wrote it)
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) { const int c = it * G + lane; if (c < ld) upd[j * ld + c] = rv.v[it]; }
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) {                      // fixed-order reduction of the loss partials
-        double s = 0.0;
-        for (int i = threadIdx.x; i < n_partials; i += 64) s += ws.partials[i];
-        s = oea::wave_sum_d(s);
-        if (threadIdx.x == 0) *loss_accum += s;
-    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) add_loss_partials_wave(ws, n_partials, loss_accum);
 }
 
 __global__ void part_unpack_kernel(float *__restrict__ ent, int64_t n_ent, int ld, int world, int rank, int64_t rpr,
@@ -2084,13 +2006,7 @@ __global__ __launch_bounds__(256) void halo_apply_kernel(float *__restrict__ ent
     for (int64_t w = grp; w < rpr + n_rel; w += ngrp) {
         Row<G, IT> rv, rg, ra;
         if (w >= rpr) {
-            const int64_t r = w - rpr;
-            if (rel_x[n_rel * ld + r] == 0) continue;
-            load_row<G, IT>(rel + r * ld, ld, lane, rv);
-            load_grad_row<G, IT>(rel_x + r * ld, ld, lane, rg);
-            if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row<G, IT>(rel_acc + r * ld, ld, lane, ra);
-            flag_t dummy;
-            apply_one_row<G, IT>(rel + r * ld, rel_acc + r * ld, rel_x + r * ld, &dummy, ld, lane, cfg.rel_l2_norm, cfg, rv, rg, ra);
+            apply_exchanged_relation_row<G, IT>(w - rpr, rel, rel_acc, n_rel, ld, lane, rel_x, cfg, rv, rg, ra);
             continue;
         }
         const int64_t j = w, id = j * world + rank;
@@ -2099,14 +2015,9 @@ __global__ __launch_bounds__(256) void halo_apply_kernel(float *__restrict__ ent
         load_row<G, IT>(v, ld, lane, rv);
         load_grad_row<G, IT>(ws.ent_grad + id * ld, ld, lane, rg);
         if (cfg.opt_kind == OEA_OPT_ADAGRAD) load_row<G, IT>(acc_own + j * ld, ld, lane, ra);
-        apply_one_row<G, IT>(v, acc_own + j * ld, ws.ent_grad + id * ld, ws.ent_touched + id, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
+        apply_one_row(v, acc_own + j * ld, ws.ent_grad + id * ld, ws.ent_touched + id, ld, lane, cfg.ent_l2_norm, cfg, rv, rg, ra);
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) {                      // fixed-order reduction of the loss partials
-        double s = 0.0;
-        for (int i = threadIdx.x; i < n_partials; i += 64) s += ws.partials[i];
-        s = oea::wave_sum_d(s);
-        if (threadIdx.x == 0) *loss_accum += s;
-    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) add_loss_partials_wave(ws, n_partials, loss_accum);
 }
 
 // relation rows of the scratch (copies folded by the GRAD phase) + flags -> rel_x, scratch cleared (part_pack_kernel's relation half)
@@ -2174,8 +2085,13 @@ void launch_wave(int nb, int block, hipStream_t st, const float *ent, const floa
     static const int dbg = [] { const char *e = getenv("OEA_STEP_WAVE_DBG"); return e ? atoi(e) : 0; }();
 #define OEA_WAVE(L1, KT)                                                                                                               \
     do {                                                                                                                               \
-        if (contrib) oea::launch_timed(triple_wave<IT64, L1, KT, true>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, order);   \
-        else oea::launch_timed(triple_wave<IT64, L1, KT, false>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, nullptr);          \
+        if constexpr (!oea::kDetScratch) {  /* PLAN = true: where a plan can exist (kPlanInstance) */                                  \
+            if (contrib) {                                                                                                             \
+                oea::launch_timed(triple_wave<IT64, L1, KT, true>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, order);   \
+                break;                                                                                                                 \
+            }                                                                                                                          \
+        }                                                                                                                              \
+        oea::launch_timed(triple_wave<IT64, L1, KT, false>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, nullptr);   \
     } while (0)
     if (k == 10) { if (cfg.l1) OEA_WAVE(1, 10); else OEA_WAVE(0, 10); }
     else { if (cfg.l1) OEA_WAVE(1, 0); else OEA_WAVE(0, 0); }
@@ -2199,6 +2115,13 @@ static bool wave_rule(const oea_step_cfg &cfg, int64_t n_ent, int64_t n_rel, int
            !step_runtime_kind();
 }
 
+// The instances of for_row_width's ladder that wave_rule can send to triple_wave (ld <= 256), and with them the plan's: the kernels
+// of a planned step are built for these alone, and in the fp32 build alone (oea_step_plan_supported refuses the fixed-point build)
+template <int G, int IT>
+constexpr bool kWaveInstance = (G == 32 && IT <= 4) || (G == 64 && IT == 4);
+template <int G, int IT>
+constexpr bool kPlanInstance = kWaveInstance<G, IT> && !oea::kDetScratch;
+
 template <int G, int IT>
 void launch_grouped(int nb, int block, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
                     int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, bool wave, float *contrib = nullptr,
@@ -2207,7 +2130,7 @@ void launch_grouped(int nb, int block, hipStream_t st, const float *ent, const f
     const int k = cfg.neg_group_k;
     // one wave per positive (round 6) where wave_rule says so (wave = its answer; ld <= 256 are exactly the instances below): same
     // grid as triple_grouped with blocks of (256 / G) waves, so the number of loss partials is launch_step's nb1 either way
-    if constexpr ((G == 32 && IT <= 4) || (G == 64 && IT == 4)) {
+    if constexpr (kWaveInstance<G, IT>) {
         if (wave) {
             constexpr int IT64 = G == 32 ? (IT + 1) / 2 : 4;
             // G == 32 (ld <= 128): the grid has one workgroup per 8 positives (launch_step's rule for the loss partials).  512 threads =
@@ -2360,30 +2283,32 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
             // (gpurun_out r02p).  OEA_APPLY_G16 = 0 / 1 overrides the size rule.
             const bool g16 = apply_g16(n_ent, n_rel, ld);
             if (plan) {
-                // ONE launch: relation rows | the plan's rows (gathered sums) | flagged rows the plan does not list | loss partials
-                static_assert(kMaxBlocks <= 16 * 256, "the partials block reads 16 per lane");
-                const int64_t bound = 2 * n_pos;                       // at most two distinct rows per positive
-                const int pgpb = g16 && G == 32 ? 16 : gpb;
-                const int relb = (int)std::max<int64_t>(oea::ceil_div(n_rel, pgpb), 1);
-                const int planb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(bound, pgpb), 1), 8192);
-                const int scanb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_ent, 256), 1), 4096);
-                auto launch = [&](auto kernel) {
-                    oea::launch_events(kernel, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg,
-                                       ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b, plan->step_first, plan_step,
-                                       plan->inplan, plan->contrib);
-                };
-                if (g16 && G == 32)
-                    for_width16(ld, [&](auto it) {
-                        constexpr int IT16 = decltype(it)::value;
-#ifndef OEA_DET_SCRATCH
-                        // rows as float4 (apply_step_plan_v4); OEA_APPLY_V4=0: dword fragments
-                        static const bool v4 = [] { const char *e = getenv("OEA_APPLY_V4"); return !(e && e[0] == '0'); }();
-                        if (v4) return launch(apply_step_plan_v4<16, IT16>);
-#endif
-                        launch(apply_step_plan<16, IT16>);
-                    });
-                else
-                    launch(apply_step_plan<G, IT>);
+                if constexpr (kPlanInstance<G, IT>) {
+                    // ONE launch: relation rows | the plan's rows (gathered sums) | flagged rows the plan does not list | loss partials
+                    const int64_t bound = 2 * n_pos;                       // at most two distinct rows per positive
+                    const int pgpb = g16 && G == 32 ? 16 : gpb;
+                    const int relb = (int)std::max<int64_t>(oea::ceil_div(n_rel, pgpb), 1);
+                    const int planb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(bound, pgpb), 1), 8192);
+                    const int scanb = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_ent, 256), 1), 4096);
+                    auto launch = [&](auto kernel) {
+                        oea::launch_events(kernel, relb + planb + scanb + 1, block, st, ev0, ev1, ent, ent_acc, n_ent, rel, rel_acc, n_rel, ld, cfg,
+                                           ws, n_part, loss_accum, folded, relb, scanb, plan->recs, plan->vals_b, plan->step_first, plan_step,
+                                           plan->inplan, plan->contrib);
+                    };
+                    if (g16 && G == 32)
+                        for_width16(ld, [&](auto it) {
+                            constexpr int IT16 = decltype(it)::value;
+                            // rows as float4; OEA_APPLY_V4=0: dword fragments
+                            static const bool v4 = [] { const char *e = getenv("OEA_APPLY_V4"); return !(e && e[0] == '0'); }();
+                            if (v4) launch(apply_step_plan<16, IT16, true>);
+                            else launch(apply_step_plan<16, IT16, false>);
+                        });
+                    else
+                        launch(apply_step_plan<G, IT, false>);
+                } else {
+                    oea::set_error("a plan for a row width no planned kernel is built for (ld %d)", ld);
+                    return OEA_EUNSUPPORTED;
+                }
             } else
             if (g16 && G == 32 && R == 1) {
                 const int nbg = (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_rel + n_ent, 16), 1), 16384);

@@ -7,7 +7,7 @@ instead of as 1 + k independent triples.  Here EVERY positive is such a positive
 
 What runs: the per-step API (`ops.triple_step`: `triple_wave<..., PLAN = false>` + `apply_rows`) in this process, and the planned
 epoch call (`ops.triple_epoch` with a plan buffer under OEA_STEP_PLAN=2: `triple_wave<..., PLAN = true>` with the relation order +
-`apply_step_plan*`) in one worker process, as tests/test_step_plan_gpu.py does it.  The other side is `oracle.cport.triple_step`
+`apply_step_plan<G, IT, V4>`) in one worker process, as tests/test_step_plan_gpu.py does it.  The other side is `oracle.cport.triple_step`
 (C, double accumulation) on the same batch.  Limits as in tests/test_step_plan_gpu.py: rows `_tol.assert_rows_close` at 1e-4,
 accumulators rtol 2e-3 / atol 1e-6, loss 1e-5 relative, rows no triple names keep their bits, scratch and flags zero afterwards.
 
@@ -184,7 +184,7 @@ def test_step_api_foreign_entry_among_mixed_positives(ops, capsys):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the planned epoch call: triple_wave<..., PLAN = true> + apply_step_plan*, one worker process under OEA_STEP_PLAN=2
+# the planned epoch call: triple_wave<..., PLAN = true> + apply_step_plan<G, IT, V4>, one worker process under OEA_STEP_PLAN=2
 # ---------------------------------------------------------------------------------------------------------------------------------
 
 

@@ -190,7 +190,7 @@ def zipf_relations(c, pos, neg):
 
 def test_default_dispatch_at_the_100k_shape_across_an_epoch_boundary(ops, monkeypatch, capsys):
     """EN-FR-100K shape (200,000 entities, 700 relations with Zipf weights, d 100, k 10), no switch set: `triple_wave<2, 0, 10, true>`
-    with the order, `apply_step_plan_v4<16, 7>`.  Epoch A = batches of 20,000 and 19,825; epoch B = 19,825 and 20,000 other positives:
+    with the order, `apply_step_plan<16, 7, true>`.  Epoch A = batches of 20,000 and 19,825; epoch B = 19,825 and 20,000 other positives:
     its plan is built into the SAME buffer, over A's.  Four teacher-forced Adagrad steps; the tables, the accumulators, the workspace
     and the plan buffer carry over the boundary.  From the device's rel_order: the (workgroup of 8, relation) groups of every step
     are below 25 % of its positives (the issue counted 15.6 % on the bench's KG), in batch order above 75 % (84 %)."""

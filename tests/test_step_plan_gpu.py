@@ -1,7 +1,7 @@
 """The PLANNED translational step against the C oracle, in every dispatch.
 
 What runs: `triple_wave<..., PLAN = true>` (a positive's two gradient rows leave as plain stores into `contrib`) and the optimiser
-of a planned step, `apply_step_plan_v4<16, IT>` / `apply_step_plan<16, IT>` / `apply_step_plan<G, IT>` (sums `contrib` rows in
+of a planned step, `apply_step_plan<16, IT, true>` / `apply_step_plan<16, IT, false>` / `apply_step_plan<G, IT, false>` (sums `contrib` rows in
 the plan's order, adds the atomic scratch where a row's touched flag is up, scans the flags for rows the plan does not list,
 updates the relation rows, adds the loss partials), driven through the C ABI as the epoch engine drives them
 (`ops.triple_epoch` with presampled negatives and a plan buffer), on negatives made HERE.  The other side is
@@ -22,6 +22,9 @@ names and 3 % of its relation rows may be left out; above that the test fails.  
 Branch counts.  For every step the test counts, in numpy from the oracle's state before the step: positives outside the plan's
 rule, rows the plan lists, hub rows (more than 8 references), listed rows whose touched flag is up (the merge branch) and flagged
 rows the plan does not list (the flag scan); it prints them and asserts they are above zero where a case is meant to cover them.
+
+Run to run.  `test_planned_rows_keep_their_bits_run_to_run` needs no oracle: with no negative active, the rows whose whole gradient is
+the plan's gathered sum must have the same bits when a step is repeated from the same state.
 """
 import ctypes as C
 import json
@@ -54,10 +57,11 @@ def ops():
 
 
 def case(name, n_ent=6000, n_rel=200, d=75, sizes=(3000, 0, 2500, 64), k=5, norm="L2", opt="Adagrad", neg_margin=3.0, pos_margin=0.01,
-         seed=1, uniform=False, calls=None):
-    """calls: None = every step in a call of its own, teacher-forced; a list of (lo, hi) = those ranges, free-running"""
+         seed=1, uniform=False, calls=None, repeat=False):
+    """calls: None = every step in a call of its own, teacher-forced; a list of (lo, hi) = those ranges, free-running.
+    repeat: no oracle -- every step twice from the same device state (worker_repeat)"""
     return dict(name=name, n_ent=n_ent, n_rel=n_rel, d=d, sizes=list(sizes), k=k, norm=norm, opt=opt, neg_margin=neg_margin,
-                pos_margin=pos_margin, seed=seed, uniform=uniform, calls=calls)
+                pos_margin=pos_margin, seed=seed, uniform=uniform, calls=calls, repeat=repeat)
 
 
 def make_batches(c):
@@ -184,6 +188,9 @@ def worker_main():
         pos, neg, offsets = make_batches(c)
         run = DeviceRun(ops, c, pos, neg, offsets, make_tables(c))
         out["%d_supported" % ci] = run.supported
+        if c["repeat"]:
+            worker_repeat(run, ci, c, out)
+            continue
         for j, (lo, hi) in enumerate(calls_of(c)):
             if c["calls"] is None and j > 0:
                 run.set_state([inp["%d_%d_%d" % (ci, j - 1, a)] for a in range(4)])
@@ -193,6 +200,25 @@ def worker_main():
             out["%d_%d_misc" % (ci, j)] = np.array([loss, pad_ok, ws_ok], np.float64)
         del run
     np.savez(os.environ["OEA_OUT"], **out)
+
+
+def worker_repeat(run, ci, c, out):
+    """every step of a repeat case TWICE from the same tables, accumulators, workspace, plan and `contrib` (the plan buffer holds both).
+    A first call builds the plan and is thrown away.  Every step starts from the case's initial tables: the same in every process.
+    -> "<ci>_<s>_<a>p": array a before the step, "..._<a>": after the first run, "..._<a>b": after the second"""
+    before = [t[:, :run.d].cpu().numpy() for t in (run.e, run.ea, run.r, run.ra)]
+    run.run(0, 1)
+    for s in range(len(c["sizes"])):
+        run.set_state(before)
+        ws0, plan0 = run.ws.clone(), run.plan.clone()
+        first = run.run(s, s + 1)
+        run.set_state(before)
+        run.ws.copy_(ws0)
+        run.plan.copy_(plan0)
+        second = run.run(s, s + 1)
+        for a in range(4):
+            out["%d_%d_%dp" % (ci, s, a)], out["%d_%d_%d" % (ci, s, a)], out["%d_%d_%db" % (ci, s, a)] = before[a], first[0][a], second[0][a]
+        out["%d_%d_misc" % (ci, s)] = np.array([first[1], first[2], first[3], second[1], second[2], second[3]], np.float64)
 
 
 WORKER = r'''
@@ -359,7 +385,7 @@ def run_worker(tmp_path, tag, env_extra, cases):
         return _WORKERS[tag]
     inp = {"cases": np.array(json.dumps(cases))}
     for ci, c in enumerate(cases):
-        if c["calls"] is None:
+        if c["calls"] is None and not c["repeat"]:
             pos, neg, offsets = make_batches(c)
             for s, _, after, _, _ in oracle_steps(c, pos, neg, offsets)[:-1]:      # (nothing starts from the last step's state)
                 for a in range(4):
@@ -394,7 +420,7 @@ def run_worker(tmp_path, tag, env_extra, cases):
 def test_default_dispatch_at_the_100k_shape(ops, neg_margin, capsys):
     """EN-FR-100K shape (200,000 entities, 700 relations, d 100, three batches of 20,000, k 10), no switch set: tables + state of
     241 MB make the library choose the plan, 16-lane groups and float4 rows (`triple_wave<2, 0, 10, true>`,
-    `apply_step_plan_v4<16, 7>`).  Three teacher-forced Adagrad steps.  neg_margin 2.0: few negatives are active (the merge branch
+    `apply_step_plan<16, 7, true>`).  Three teacher-forced Adagrad steps.  neg_margin 2.0: few negatives are active (the merge branch
     and the flag scan see a few hundred rows); 3.0: about half of them are (thousands of rows in both)."""
     c = case("100k", n_ent=200000, n_rel=700, d=100, sizes=(20000, 20000, 20000), k=10, neg_margin=neg_margin, seed=7)
     pos, neg, offsets = make_batches(c)
@@ -449,9 +475,25 @@ ENVS = {"g0": dict(OEA_STEP_PLAN="2", OEA_APPLY_G16="0"),
         "atomic-g16": dict(OEA_STEP_PLAN="0", OEA_APPLY_G16="1")}
 
 
+REPEAT_ENVS = ("g0", "g16", "g16-dword")
+
+
+def repeat_cases():
+    """test_planned_rows_keep_their_bits_run_to_run: one batch of 3,000 and one of 64 (the batch's last workgroup), k 5, and
+    neg_margin 0.0: the limited loss makes a negative active only when neg_margin - s > 0, and s >= 0, so NO negative is active and
+    an entity row receives an atomic only as a hub or from a positive outside the plan's rule.  d 24: a float4 fragment that only
+    lanes 0-5 fill; d 100: the second float4 fragment ends at lane 8, and the dword row has seven fragments; d 128: a full row;
+    d 200: the 64-lane kernel -- the smallest shapes at which a fragment's bound or a lane group's tail can go wrong"""
+    kw = dict(sizes=(3000, 64), k=5, pos_margin=0.01, neg_margin=0.0, repeat=True)
+    return [case("repeat-d%d" % d, d=d, seed=700 + d, **kw) for d in (24, 100, 128, 200)] + \
+           [case("repeat-d100-sgd", d=100, opt="SGD", seed=801, **kw)]
+
+
 def env_cases(env):
     """what the worker process of a set of switches runs"""
     cs = small_cases() + (edge_cases() if env in ("g0", "g16") else [])
+    if env in REPEAT_ENVS:
+        cs += repeat_cases()
     if env == "g0":
         cs.append(case("ranges", d=75, k=5, neg_margin=2.0, seed=501, calls=[(0, 2), (2, 4)]))
     return cs
@@ -459,8 +501,8 @@ def env_cases(env):
 
 @pytest.mark.parametrize("env", sorted(ENVS))
 def test_every_instance_and_the_grid_stride_edges(env, tmp_path, capsys):
-    """OEA_STEP_PLAN=2 (the plan whatever the table size) with 32-lane groups (`apply_step_plan<32, 1..4>`, `<64, 4>`), 16-lane groups
-    and float4 rows (`apply_step_plan_v4<16, 2|4|5|6|7|8>`), 16-lane groups and dword fragments (`apply_step_plan<16, ...>`):
+    """OEA_STEP_PLAN=2 (the plan whatever the table size) with 32-lane groups (`apply_step_plan<32, 1..4, false>`, `<64, 4, false>`), 16-lane groups
+    and float4 rows (`apply_step_plan<16, 2|4|5|6|7|8, true>`), 16-lane groups and dword fragments (`apply_step_plan<16, ..., false>`):
     small_cases() on 6,000 entities in batches of 3,000 / 0 (empty) / 2,500 / 64, teacher-forced; in the first two also
     edge_cases(), where a grid-stride loop of the optimiser kernel runs more than once.
     "atomic-g16": OEA_STEP_PLAN=0 with 16-lane groups -- no plan, every gradient through the atomic scratch and the flag-driven
@@ -470,7 +512,7 @@ def test_every_instance_and_the_grid_stride_edges(env, tmp_path, capsys):
         print()
         out, factory = run_worker(tmp_path, env, ENVS[env], cases)
         for ci, c in enumerate(cases):
-            if c["calls"] is not None:                               # test_step_ranges_across_calls
+            if c["calls"] is not None or c["repeat"]:                # test_step_ranges_across_calls, test_planned_rows_keep_...
                 continue
             assert bool(out["%d_supported" % ci]) == (env != "atomic-g16"), c["name"]
             tag = "%s %s" % (env, c["name"])
@@ -522,3 +564,76 @@ def test_plan_and_scoring_kernel_are_chosen_by_one_rule(tmp_path, capsys):
         out, factory = run_worker(tmp_path, "kind", dict(OEA_STEP_PLAN="2", OEA_STEP_RUNTIME_KIND="1"), [c])
         print("OEA_STEP_RUNTIME_KIND=1: step_plan_supported = %s" % bool(out["0_supported"]))
         check_case("runtime-kind", c, factory(0), ("outside", "listed", "hubs", "merge", "scan"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# case 6: rows summed from the plan have the same bits run to run
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+
+def planned_only_rows(c, pos, neg):
+    """of one step, in numpy from the batch -> (rows whose whole gradient is the plan's gathered sum when no negative is active: named
+    as head or tail by positives inside the plan's rule only, at most HUB_ENTRIES times; rows the step's positives name; rows only its
+    negatives name; every row it names).  Left out of the first: hubs, and every row a positive outside the rule or one of its
+    negatives names (their gradients go through the atomic scratch)"""
+    n_ent, k = c["n_ent"], c["k"]
+    p64, ng = pos.astype(np.int64), neg.reshape(len(pos), k, 3).astype(np.int64)
+    same_h, same_t, same_r = ng[:, :, 0] == p64[:, :1], ng[:, :, 2] == p64[:, 2:], ng[:, :, 1] == p64[:, 1:2]
+    inrule = (same_r & (same_h | same_t)).all(1) & (same_h.all(1) | same_t.all(1))
+    refs = np.bincount(np.concatenate([p64[inrule, 0], p64[inrule, 2]]), minlength=n_ent)
+    outside = np.zeros(n_ent, bool)
+    outside[p64[~inrule][:, [0, 2]].ravel()] = True
+    outside[ng[~inrule][:, :, [0, 2]].ravel()] = True
+    by_pos, by_neg = np.zeros(n_ent, bool), np.zeros(n_ent, bool)
+    by_pos[p64[:, [0, 2]].ravel()] = True
+    by_neg[ng[:, :, [0, 2]].ravel()] = True
+    return (refs > 0) & (refs <= HUB_ENTRIES) & ~outside, by_pos, by_neg & ~by_pos, by_pos | by_neg
+
+
+def check_repeat(env, cases, out):
+    """the assertions of test_planned_rows_keep_their_bits_run_to_run on the output of a worker that ran `cases`"""
+    seen = 0
+    for ci, c in enumerate(cases):
+        if not c["repeat"]:
+            continue
+        seen += 1
+        assert bool(out["%d_supported" % ci]), c["name"]
+        pos, neg, offsets = make_batches(c)
+        n_keep = n_named = 0
+        for s in range(len(c["sizes"])):
+            lo, hi = int(offsets[s]), int(offsets[s + 1])
+            keep, by_pos, only_neg, named = planned_only_rows(c, pos[lo:hi], neg[lo * c["k"]: hi * c["k"]])
+            tag = "%s %s step %d" % (env, c["name"], s)
+            before, first, second = ([out["%d_%d_%d%s" % (ci, s, a, sfx)] for a in range(2)] for sfx in ("p", "", "b"))
+            misc = out["%d_%d_misc" % (ci, s)]
+            assert misc[1] and misc[2] and misc[4] and misc[5], "%s: pad columns / scratch not clean after a run" % tag
+            for got in (first, second):
+                assert _same_bits(got[0][only_neg], before[0][only_neg]) and _same_bits(got[1][only_neg], before[1][only_neg]), \
+                    "%s: a row that only negatives name moved: a negative was active" % tag
+            moved = (first[0][keep] != before[0][keep]).any(1)
+            print("%s: %d rows compared of %d the positives name (%d named in all, %d by negatives only); %d of them moved; "
+                  "loss %.6f / %.6f" % (tag, keep.sum(), by_pos.sum(), named.sum(), only_neg.sum(), moved.sum(), misc[0], misc[3]))
+            assert 2 * keep.sum() > by_pos.sum() and 2 * moved.sum() > keep.sum(), "%s: the compared set is too small" % tag
+            assert _same_bits(first[0][keep], second[0][keep]), "%s: planned entity rows differ between two runs" % tag
+            assert _same_bits(first[1][keep], second[1][keep]), "%s: planned accumulator rows differ between two runs" % tag
+            n_keep, n_named = n_keep + int(keep.sum()), n_named + int(named.sum())
+        assert 2 * n_keep > n_named, "%s %s: %d rows compared of %d named" % (env, c["name"], n_keep, n_named)
+    assert seen == 5
+
+
+@pytest.mark.parametrize("env", REPEAT_ENVS)
+def test_planned_rows_keep_their_bits_run_to_run(env, tmp_path, capsys):
+    """step_plan.h promises "no atomics, no order dependence" for the rows the plan sums.  repeat_cases() under the 32-lane, the
+    16-lane float4 and the 16-lane dword switches: every step runs twice from the same tables, accumulators, workspace, `contrib` and
+    plan (worker_repeat), and the entity rows and accumulator rows of planned_only_rows() must come out with the same BITS.  No
+    oracle, no tolerance.  Relation rows and every other entity row are not compared: their sums go through atomics.
+    That no negative was active is read from the device's own numbers: a row that only negatives name keeps its bits through the
+    step (an active negative moves the row it corrupts).
+    The compared set must be more than half of the rows the step's positives name, and over the case's two steps more than half of
+    ALL the rows they name, negatives' included (2,884 of 5,062 at d 24; the batch of 64 alone cannot reach that: its 320
+    negatives name about 210 rows that no positive names, against about 115 that its positives name), and most of it must move."""
+    cases = env_cases(env)
+    with capsys.disabled():
+        print()
+        out, _ = run_worker(tmp_path, env, ENVS[env], cases)
+        check_repeat(env, cases, out)
