@@ -4,7 +4,7 @@
 //     sim_mat = np.matmul(sub_embed, embed.T); np.argpartition(-sim_mat[i], k)[:k]
 // k is large here (int((1-eps)*N): 1,499 of 15,000; 2,000 of 100,000), so instead of keeping k
 // candidates per row on chip the search is a per-row SELECT on the fp32 keys:
-//   1. a strip of rows of S is produced by the MFMA tile kernel (sim_rank.hip) into an HBM
+//   1. a strip of rows of S is produced by the MFMA tile kernel (sim_inner_store_packed, sim_tiles.h) into an HBM
 //      workspace (strips of a few thousand rows: a full wave of workgroups per launch matters more than
 //      keeping the strip in the 256 MB Infinity Cache -- see ops.topk_inner),
 //   2. one workgroup per row, three coalesced reads of the row (16 B per lane):
@@ -22,13 +22,16 @@
 //
 // Which path oea_topk_inner takes (all give the same result):
 //   queries == candidates, 12,288 <= N <= 131,072   stream form: sampled thresholds; upper-triangle tile sweep on the bf16
-//                                                   hi / lo split writing per-wave record streams (sim_rank.hip:
-//                                                   topk_stream_sym_kernel, redo list + overflow pool for crowded waves);
+//                                                   hi / lo split writing per-wave record streams
+//                                                   (topk_stream_sym_kernel, redo list + overflow pool for crowded waves);
 //                                                   topk_bucket_kernel -> compact per-row lists; list_select_kernel (exact
 //                                                   chains around the k-th approximate value); strip fallback for failed rows
 //   nc >= 32,768, nq >= 4,096                       per-query segment lists from the full sweep (bf16 hi / lo split; OEA_TOPK_BF16=0:
 //                                                   fp32) -- also queries == candidates outside the stream form's range
 //   otherwise                                       N x N strips + per-row select (above)
+//
+// This file holds the whole search: the select kernels, the sweep kernels of the list and stream forms (on the tile pipelines of
+// sim_tiles.h), their plans, launch rules and OEA_TOPK_* switches, and oea_topk_inner / oea_topk_rows / oea_row_rank_select_*.
 #include <math.h>
 #include <stdlib.h>
 
@@ -36,14 +39,11 @@
 
 #include <vector>
 
-#include "common.h"
+#include "sim_tiles.h"
+
+using namespace oea;
 
 namespace {
-
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    uint32_t u = __float_as_uint(f + 0.0f);   // -0 -> +0 so that key order == float order
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 constexpr int SEL_THREADS = 256;
 
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(SEL_THREADS) void row_select_sampled_kernel(const f
 // ---- strip-free search for long candidate lists ---------------------------------------------------------------------
 // (1) thr[q] = the r-th largest similarity of query q to a strided SAMPLE of kSample candidates: with r a little above
 //     k * kSample / nc (3 sigma + slack) the whole row holds >= k values at or above it, and only ~1.35 k of them;
-// (2) the tile sweep appends exactly those survivors to per-query list segments (sim_rank.hip: topk_append_kernel) --
+// (2) the tile sweep appends exactly those survivors to per-query list segments (topk_append_kernel) --
 //     the nq x nc strip is never written (it was 2 x 40 GB of traffic at 100,000 x 100,000);
 // (3) list_select_kernel picks the exact top-k by (value desc, column asc) among a query's survivors in LDS and writes
 //     them in ascending column order (bitonic sort of the k selected columns);
@@ -725,6 +725,8 @@ constexpr int kMaxSeg = 256;              // query-side segments per row
 constexpr int kSpillCap = 512;             // entries of a row's spill list (appends that found their segment full)
 constexpr int kMaxSegAll = kMaxSeg + 1;   // + the row's spill list: every segment list_select_kernel scans (sizes its registers and LDS)
 
+// sim_tiles.h's ord2f, hidden here by this file's own spelling of it (& where that one has ^: the same function, but hipcc compiles
+// kth_value_kernel and list_select_kernel to other code from the other spelling -- list_select_kernel to 20 B of scratch for 12)
 __device__ __forceinline__ float ord2f(uint32_t key) {
     return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
 }
@@ -806,8 +808,92 @@ __global__ __launch_bounds__(256) void kth_value_kernel(const float *__restrict_
     if (lane == 0) thr[row] = ord2f(prefix);
 }
 
+// ---- threshold-append epilogue (strip-free neighbour search): M = candidates, N = queries ------------------------------
+// Same sweep as rank_inner_kernel (sim_rank.hip); the epilogue keeps only the similarities at or above the query's threshold thr[q]
+// (estimated from a column sample, so that a few thousand of the n2 candidates survive) and appends (value, column) to a
+// list segment PRIVATE to the lane: a query's survivors of chunk y come from the two wave rows (wm) and the two half-waves
+// that share it, hence 4 * gridDim.y segments of `cap` entries per query, each in ascending column order.  No atomics, no
+// N x N strip in HBM.  Values and columns go to two arrays (one dword store each from the register that holds them) at a
+// 32-bit byte offset from a wave-uniform base.  counts[q * nseg + seg] may exceed cap: the entries past cap went to the
+// query's spill list (one global atomic each; rare unless the neighbours of a row crowd into one candidate range).
+// BF16 (round 6): q / c are the hi / lo split packed rows (ldq = ldc = Kp), the sweep runs on the bf16 matrix pipe and the lists hold
+// every pair with v~ >= thr - tol (tol = *tol_ptr bounds |v~ - v|): list_select_kernel decides the neighbourhood of the k-th value
+// with exact chains -- the same sets as the fp32 sweep
+// NCH > 0 (BF16 only): the query operand in registers (tile_pipeline_bf16_breg, Kp = 32 NCH)
+template <bool BF16 = false, int NCH = 0>
+__global__ __launch_bounds__(256, 2) void topk_append_kernel(
+    const float *__restrict__ q, int64_t nq, int ldq, const float *__restrict__ c, int64_t nc, int ldc, int dim,
+    const float *__restrict__ thr, int tiles_per_chunk, int cap, float *__restrict__ list_vals, int32_t *__restrict__ list_cols,
+    int32_t *__restrict__ counts, int32_t *__restrict__ spill_cnt, uint2 *__restrict__ spill, int sp_cap,
+    const float *__restrict__ tol_ptr = nullptr) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * TILE * LDS_LD];          // one array: the register form uses it as 2 x 2 chunks of A
+    float *As = lds, *Bs = lds + 2 * TILE * LDS_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int64_t q0 = (int64_t)blockIdx.x * TILE;
+    const int64_t nct = (nc + TILE - 1) / TILE;
+    const int64_t ct_begin = (int64_t)blockIdx.y * tiles_per_chunk;
+    const int64_t ct_end = (ct_begin + tiles_per_chunk < nct) ? ct_begin + tiles_per_chunk : nct;
+    const int nseg = 4 * (int)gridDim.y;
+    const int sidx = ((int)blockIdx.y * 2 + wm) * 2 + (lane >> 5);
+    float th[2];
+    uint32_t boff[2], bbeg[2], blast[2];                          // byte offsets in the lane's segment from the workgroup's base
+    int64_t qi[2];
+    char *__restrict__ vbase = reinterpret_cast<char *>(list_vals + q0 * nseg * (int64_t)cap);      // wave-uniform
+    char *__restrict__ cbase = reinterpret_cast<char *>(list_cols + q0 * nseg * (int64_t)cap);
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+        const int ql = wn * 64 + tn * 32 + (lane & 31);
+        qi[tn] = q0 + ql;
+        th[tn] = qi[tn] < nq ? thr[qi[tn]] - (BF16 ? *tol_ptr : 0.f) : INFINITY;            // padding rows never append
+        bbeg[tn] = boff[tn] = 4u * (uint32_t)((ql * nseg + sidx) * cap);
+        blast[tn] = boff[tn] + 4u * (uint32_t)(cap - 1);          // survivors past cap overwrite the last slot; boff keeps counting
+    }
+    auto sweep = [&](f32x16 (&acc)[2][2], int jb, int j_end) {
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int j = jb + tm * 32 + (r & 3) + 8 * (r >> 2);       // ascending in (tm, r >> 2, r & 3)
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) {
+                    const float v = acc[tm][tn][r];
+                    if (v >= th[tn] && j < j_end) {
+                        // the store path stays branch-free: entries from index cap - 1 on land in the segment's LAST slot
+                        // (scratch: the select reads min(count, cap - 1) entries) and go to the row's spill list, one global
+                        // atomic each -- rare unless the neighbours of a row crowd into one candidate range
+                        const uint32_t at = min(boff[tn], blast[tn]);
+                        *reinterpret_cast<float *>(vbase + at) = v;
+                        *reinterpret_cast<int32_t *>(cbase + at) = j;
+                        if (boff[tn] >= blast[tn]) {
+                            const int pos = atomicAdd(spill_cnt + qi[tn], 1);
+                            if (pos < sp_cap) spill[qi[tn] * sp_cap + pos] = make_uint2(__float_as_uint(v), (uint32_t)j);
+                        }
+                        boff[tn] += 4u;
+                    }
+                }
+            }
+        }
+    };
+    auto epilogue = [&](int64_t t, f32x16 (&acc)[2][2]) {
+        const int64_t c0 = (ct_begin + t) * TILE;
+        const int jb = (int)c0 + wm * 64 + 4 * (lane >> 5);
+        if (c0 + TILE <= nc) sweep(acc, jb, 0x7fffffff);          // interior tile: the bound folds away
+        else sweep(acc, jb, (int)nc);
+    };
+    const int64_t n_tiles = ct_end > ct_begin ? ct_end - ct_begin : 0;
+    auto m_tile = [=](int64_t t) { return (ct_begin + t) * TILE; };
+    if constexpr (BF16 && NCH > 0) tile_pipeline_bf16_breg<NCH>(c, ldc, q, q0, n_tiles, m_tile, As, epilogue, dim);
+    else if constexpr (BF16) tile_pipeline_bf16<false>(c, ldc, q, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
+    else tile_pipeline_packed(c, ldc, q, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+        if (qi[tn] < nq) counts[qi[tn] * nseg + sidx] = (int32_t)((boff[tn] - bbeg[tn]) >> 2);
+}
+
 constexpr int kStreamMaxT = 1024;             // target tiles: <= 131,072 rows (the slice table is (64 + 4 T) * 8 B of LDS)
-using oea::kOvfChunk;                         // records per chunk of the overflow pool (common.h)
+constexpr int kOvfChunk = 512;                // records per chunk of the stream form's overflow pool: written by topk_stream_redo_kernel,
+                                              // sized by plan_stream, read back by topk_overflow_kernel
 constexpr int kPerThread = 24;            // list entries a thread keeps in registers: lists of up to 6,144 survivors
 constexpr int kBitWords = 8192;           // bitmap of selected columns in (dynamic) LDS: nc <= 262,144
 
@@ -1111,7 +1197,7 @@ __global__ __launch_bounds__(SEL_THREADS, 5) void list_select_kernel(const float
     if (tid == 0) fail_rows[atomicAdd(n_fail, 1)] = (int32_t)row;
 }
 
-// ---- gather of <= kFbRows failed rows (the CSLS means' bulk fallback, sim_rank.hip) ---------------------------------------
+// ---- gather of <= kFbRows failed rows (the CSLS means' bulk fallback, csls_means.hip) -------------------------------------
 constexpr int kFbRows = 128;
 
 __global__ void gather_fail_rows_kernel(const float *__restrict__ qp, int kp, const int32_t *__restrict__ fail_rows,
@@ -1174,7 +1260,8 @@ static ListPlan plan_lists(int64_t nq, int64_t nc, int k, size_t ws_bytes) {
     if (ws_bytes <= fixed) return p;
     int64_t rows = nq;
     for (int iter = 0; iter < 8; ++iter) {
-        const int chunks = oea::topk_append_chunks(rows, nc);
+        int tpc_unused;
+        const int chunks = pick_chunks(ceil_div(rows, TILE), ceil_div(nc, TILE), &tpc_unused);    // so that the grid fills the chip
         const int nseg = 4 * chunks;
         if (nseg > kMaxSeg) return p;
         const double m = m_total / nseg;
@@ -1310,8 +1397,302 @@ __global__ void sym_items_kernel(int T, int L, int chunks, int4 *__restrict__ it
     items[base + qt] = make_int4(qt, max(qt, c * L), min(T, (c + 1) * L), c - qt / L);
 }
 
+// ---- stream form of the symmetric neighbour sweep (round 4) ------------------------------------------------------------------
+// queries == candidates, S = E E^T: only the tiles on and above the diagonal are computed (bitwise S_ij == S_ji: the k-ordered
+// chain multiplies the same pairs in the same order).  A work item = (query tile qt, candidate tiles [ct_begin, ct_end) with
+// ct_begin >= qt); its tiles feed BOTH sides: the rows of tile qt, and -- off the diagonal -- row j of tile ct, which receives
+// (S_ji, i) for the rows i of tile qt.  e = the bf16 hi / lo split rows (pack_rows_bf16_kernel): the values recorded are v~ with
+// |v~ - v| <= *tol_ptr and the cut is thr - tol, so every pair whose EXACT value reaches thr is recorded (the select resolves
+// the neighbourhood of the k-th value with exact chains, list_select_kernel).  Every WAVE owns two
+// append-only streams of 8-byte records (value bits, tag): survivors of the query side (v~ >= cut of the query; tag = local
+// query row << 24 | candidate) and of the candidate side (v~ >= cut of the candidate; tag = local candidate row << 24 |
+// query), slots = stream position + prefix of a ballot -- full-line stores, no per-lane bookkeeping.  The candidate stream's
+// position at every tile boundary is kept (col_off), so that the records aimed at one candidate tile can be found again:
+// topk_bucket_kernel deals the records of one target tile to its 128 rows' compact lists, list_select_kernel selects
+// from those.  Trained tables crowd a row's neighbours into few candidate ranges, so some waves see several times the average
+// number of records.  A wave whose stream is full only notes (work item, tile, wave, positions at the tile's start) in a redo
+// list; topk_stream_redo_kernel computes those tiles again and puts the records that did not fit (stream_ovf_tile: same ballots,
+// same positions), as self-describing 16-byte records (value, target row, other index), into 512-record chunks taken from a
+// shared pool with one atomic per chunk; topk_overflow_kernel appends them to the compact lists after the bucketing.
+// (Handling the overflow inside the sweep -- a second pass over the accumulators -- cost the sweep 1.2 ms of spills and code size
+// on tables that never overflow.)  Only a pool or redo list that runs dry marks rows as lost (row_fail): strip fallback.
+
+struct OvfState {                                    // per wave (wave-uniform)
+    uint4 *__restrict__ pool;
+    int32_t *__restrict__ alloc, *__restrict__ len;
+    uint8_t *__restrict__ row_fail;
+    uint32_t cap_chunks, chunk, used;
+};
+
+__device__ __forceinline__ void ovf_append(OvfState &o, bool over, float v, uint32_t target, uint32_t other, int lane) {
+    const unsigned long long om = __ballot(over);
+    if (om == 0ull) return;                          // wave-uniform
+    const uint32_t cnt = (uint32_t)__popcll(om);
+    if (o.used + cnt > (uint32_t)kOvfChunk) {
+        if (o.chunk < o.cap_chunks && lane == 0) o.len[o.chunk] = (int32_t)o.used;
+        uint32_t idx = 0;
+        if (lane == 0) idx = (uint32_t)atomicAdd(o.alloc, 1);
+        o.chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)idx);
+        o.used = 0;
+    }
+    if (over) {
+        const uint32_t slot = o.used + __builtin_amdgcn_mbcnt_hi((uint32_t)(om >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)om, 0u));
+        if (o.chunk < o.cap_chunks) o.pool[(size_t)o.chunk * kOvfChunk + slot] = make_uint4(__float_as_uint(v), target, other, 0u);
+        else o.row_fail[target] = 1;                 // the pool ran dry: this row goes to the strip fallback
+    }
+    o.used += cnt;
+}
+
+// second pass over a tile whose records did not all fit: identical predicates and positions, only the overflow is written
+template <bool INTERIOR>
+__device__ __forceinline__ void stream_ovf_tile(const f32x16 (&acc)[2][2], int c0, int jl0, int n, const float (&th)[2], const uint32_t (&qidx)[2],
+                                                float my_tc, int lane, uint32_t rbytes, uint32_t cbytes, uint32_t rpos, uint32_t cpos,
+                                                OvfState &o) {
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = c0 + jl0 + tm * 32 + (r & 3) + 8 * (r >> 2);
+            const float tc = __shfl(my_tc, (lane & 32) + tm * 16 + r, 64);
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn) {
+                const float v = acc[tm][tn][r];
+                const bool pr = INTERIOR ? v >= th[tn] : (v >= th[tn] && j < n);
+                unsigned long long m = __ballot(pr);
+                uint32_t at = rpos + 8u * __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                ovf_append(o, pr && at >= rbytes, v, qidx[tn], (uint32_t)j, lane);
+                rpos += 8u * (uint32_t)__popcll(m);
+                const bool pc = v >= tc;
+                m = __ballot(pc);
+                at = cpos + 8u * __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                ovf_append(o, pc && at >= cbytes, v, (uint32_t)j, qidx[tn], lane);
+                cpos += 8u * (uint32_t)__popcll(m);
+            }
+        }
+    }
+}
+
+// ---- the record epilogue: no branch per accumulator (round 6) -------------------------------------------------------------------------
+// Positions and capacities are in BYTES (32-bit offsets from wave-uniform bases).  A first version branched per accumulator and side
+// (`if (pr)`: taken for 4 of 5 accumulators at k / n = 2 %, some lane of the 64 passes), each time through s_and_saveexec /
+// s_cbranch / 64-bit address arithmetic / a second compare against the capacity: ~190 cycles per accumulator and side when nothing
+// overlaps it (measured with one wave per SIMD: 24 K cycles of epilogue beside 3 K of MFMA per tile; 13.4 against 11.6 ms per
+// 100,000^2 search, and the register-operand sweep spilled with it).  Here one accumulator and side is ONE straight block: v_cmpx
+// puts the predicate into EXEC, the slot is mbcnt(EXEC), the record leaves through a raw buffer whose num_records IS the stream's
+// capacity (the hardware drops what does not fit: positions, and so the redo pass, are unchanged), the position advances on the
+// scalar unit, EXEC is restored.  5 VALU + 2 stores + 3 SALU, no branch.
+template <uint32_t TAG_ADD>
+__device__ __forceinline__ void stream_append(float v, float cut, uint32_t tag_base, __amdgpu_buffer_rsrc_t srd, uint32_t &pos,
+                                              unsigned long long full) {
+    // (the record as ONE 8-byte store from a register pair was slower: 12.4 against 11.6 ms per 100,000^2 search -- the pair costs a
+    //  copy of the accumulator for all lanes and registers the kernel does not have)
+    uint32_t c, t, cnt;
+    asm volatile(
+        "v_cmpx_ge_f32 vcc, %[v], %[cut]\n\t"
+        "s_nop 1\n\t"                                      // a VALU result in a scalar register (EXEC) read as DATA by the next VALU: 2 wait states
+        "v_mbcnt_lo_u32_b32 %[c], exec_lo, 0\n\t"
+        "v_mbcnt_hi_u32_b32 %[c], exec_hi, %[c]\n\t"
+        "v_lshl_add_u32 %[c], %[c], 3, %[pos]\n\t"
+        "v_add_u32 %[t], %[ta], %[tb]\n\t"
+        "buffer_store_dword %[v], %[c], %[srd], 0 offen\n\t"
+        "buffer_store_dword %[t], %[c], %[srd], 0 offen offset:4\n\t"
+        "s_bcnt1_i32_b64 %[cnt], exec\n\t"
+        "s_lshl3_add_u32 %[pos], %[cnt], %[pos]\n\t"
+        "s_mov_b64 exec, %[full]\n\t"
+        : [c] "=&v"(c), [t] "=&v"(t), [cnt] "=&s"(cnt), [pos] "+s"(pos)
+        : [v] "v"(v), [cut] "v"(cut), [tb] "v"(tag_base), [ta] "n"(TAG_ADD), [srd] "s"(srd), [full] "s"(full)
+        : "vcc", "scc", "memory");
+}
+
+// interior tiles (every candidate row exists); rj[tn] = rtag[tn] + c0 + jl0 and cq[tn] = (jl0 << 24) | qidx[tn] carry the lane's part of
+// the second record word, the (tm, r) part is a constant of the step I = 16 tm + r
+template <int I>
+__device__ __forceinline__ void stream_fast_steps(const f32x16 (&acc)[2][2], const float (&th)[2], const uint32_t (&rj)[2], const uint32_t (&cq)[2],
+                                                  float my_tc, bool upper, __amdgpu_buffer_rsrc_t srd_r, __amdgpu_buffer_rsrc_t srd_c,
+                                                  uint32_t &rpos, uint32_t &cpos, unsigned long long full) {
+    if constexpr (I < 32) {
+        constexpr int tm = I >> 4, r = I & 15;
+        constexpr uint32_t jc = (uint32_t)(tm * 32 + (r & 3) + 8 * (r >> 2));
+        const float t0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_tc), tm * 16 + r));
+        const float t1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_tc), 32 + tm * 16 + r));
+        const float tc = upper ? t1 : t0;
+        stream_append<jc>(acc[tm][0][r], th[0], rj[0], srd_r, rpos, full);
+        stream_append<(jc << 24)>(acc[tm][0][r], tc, cq[0], srd_c, cpos, full);
+        stream_append<jc>(acc[tm][1][r], th[1], rj[1], srd_r, rpos, full);
+        stream_append<(jc << 24)>(acc[tm][1][r], tc, cq[1], srd_c, cpos, full);
+        stream_fast_steps<I + 1>(acc, th, rj, cq, my_tc, upper, srd_r, srd_c, rpos, cpos, full);
+    }
+}
+
+__device__ __forceinline__ void stream_tile_fast(const f32x16 (&acc)[2][2], const float (&th)[2], const uint32_t (&rj)[2], const uint32_t (&cq)[2],
+                                                 float my_tc, int lane, __amdgpu_buffer_rsrc_t srd_r, __amdgpu_buffer_rsrc_t srd_c,
+                                                 uint32_t &rpos, uint32_t &cpos) {
+    const unsigned long long full = __builtin_amdgcn_ballot_w64(true);
+    stream_fast_steps<0>(acc, th, rj, cq, my_tc, lane >= 32, srd_r, srd_c, rpos, cpos, full);
+}
+
+// NCH = Kp / 32 in {1..4}: the query tile's operand in registers (tile_pipeline_bf16_breg); 0: both operands through LDS
+template <int NCH>
+__global__ __launch_bounds__(256, 2) void topk_stream_sym_kernel(
+    const float *__restrict__ e, int64_t n, int kp, int dim, const float *__restrict__ thr, const int4 *__restrict__ items,
+    uint2 *__restrict__ row_streams, int rcap, uint2 *__restrict__ col_streams, int ccap, int32_t *__restrict__ row_cnt,
+    int32_t *__restrict__ col_off, int lp1, uint8_t *__restrict__ row_fail, const float *__restrict__ tol_ptr,
+    int32_t *__restrict__ redo_cnt, int4 *__restrict__ redo, int redo_cap) {
+    __shared__ __attribute__((aligned(16))) float lds[NCH > 0 ? 4 * TILE * PLD : 4 * TILE * LDS_LD];
+    float *As = lds, *Bs = lds + 2 * TILE * LDS_LD;
+    const int4 item = items[blockIdx.x];                           // (qt, ct_begin, ct_end, segment group)
+    const int qt = item.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int half = lane >> 5, l32 = lane & 31;
+    const int64_t q0 = (int64_t)qt * TILE;
+    const size_t wid = (size_t)blockIdx.x * 4 + wave;
+    char *__restrict__ rs = reinterpret_cast<char *>(row_streams + wid * rcap);
+    char *__restrict__ cs = reinterpret_cast<char *>(col_streams + wid * ccap);
+    int32_t *__restrict__ coff = col_off + wid * lp1;
+    const uint32_t rbytes = 8u * (uint32_t)rcap, cbytes = 8u * (uint32_t)ccap;
+    const float tol = *tol_ptr;
+    float th[2];
+    uint32_t rtag[2], qidx[2];
+    int64_t qi[2];
+    bool q_in = true;
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+        const int ql = wn * 64 + tn * 32 + l32;
+        qi[tn] = q0 + ql;
+        q_in = q_in && qi[tn] < n;
+        th[tn] = qi[tn] < n ? thr[qi[tn]] - tol : INFINITY;
+        rtag[tn] = (uint32_t)ql << 24;
+        qidx[tn] = (uint32_t)qi[tn];
+    }
+    const bool q_all = __ballot(!q_in) == 0ull;                    // every query row of this wave exists (else: candidate side per lane)
+    const int jl0 = wm * 64 + 4 * half;
+    const int my_jl = jl0 + (l32 >> 4) * 32 + (l32 & 3) + 8 * ((l32 & 15) >> 2);
+    uint32_t rpos = 0, cpos = 0;                                   // wave-uniform, bytes
+    auto uniform_ptr = [](char *p) {                              // the wave's stream base, on the scalar unit
+        const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+        return reinterpret_cast<char *>(((uintptr_t)hi << 32) | lo);
+    };
+    const __amdgpu_buffer_rsrc_t srd_r = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(rs), 0, (int)rbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_c = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(cs), 0, (int)cbytes, 0x00020000);
+    const uint32_t cq[2] = {((uint32_t)jl0 << 24) | qidx[0], ((uint32_t)jl0 << 24) | qidx[1]};
+    float thr_pre = INFINITY;                                        // thr of this lane's candidate row in the tile about to be finished
+    {
+        const int64_t j0 = (int64_t)item.y * TILE + my_jl;
+        if (item.y < item.z && j0 < n) thr_pre = thr[j0];
+    }
+    auto epilogue = [&](int64_t t, f32x16 (&acc)[2][2]) {
+        const int ct = item.y + (int)t;
+        const int64_t c0 = (int64_t)ct * TILE;
+        const bool offdiag = ct != qt;                               // workgroup-uniform
+        const int64_t my_j = c0 + my_jl;
+        // the candidate-side cut is +inf where nothing may be recorded: on the diagonal and past the last candidate row
+        const float my_tc = (offdiag && my_j < n) ? thr_pre - tol : INFINITY;
+        {                                                            // the next tile's threshold, one tile ahead (an exposed L2 round trip
+            const int64_t nj = c0 + TILE + my_jl;                    // per tile and wave when asked for here)
+            thr_pre = (ct + 1 < item.z && nj < n) ? thr[nj] : INFINITY;
+        }
+        if (lane == 0) coff[t] = (int32_t)(cpos >> 3);
+        if (!q_all) {                                                // ragged last query tile: the (zero) rows past n must not reach
+                                                                     // the candidate lists: their accumulators become -inf
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+#pragma unroll
+                    for (int tn = 0; tn < 2; ++tn)
+                        if (qi[tn] >= n) acc[tm][tn][r] = -INFINITY;
+        }
+        const uint32_t r0 = rpos, p0 = cpos;
+        if (c0 + TILE > n) {                                         // ragged last candidate tile: rows past n never pass a cut
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((int)c0 + jl0 + tm * 32 + (r & 3) + 8 * (r >> 2) >= (int)n) { acc[tm][0][r] = -INFINITY; acc[tm][1][r] = -INFINITY; }
+        }
+        const uint32_t rj[2] = {rtag[0] + (uint32_t)((int)c0 + jl0), rtag[1] + (uint32_t)((int)c0 + jl0)};
+        stream_tile_fast(acc, th, rj, cq, my_tc, lane, srd_r, srd_c, rpos, cpos);
+        if (rpos > rbytes || cpos > cbytes) {                        // wave-uniform, rare: records of this tile did not fit
+            int slot = 0;
+            if (lane == 0) {
+                slot = atomicAdd(redo_cnt, 1);
+                if (slot < redo_cap) {
+                    redo[2 * (size_t)slot] = make_int4((int)blockIdx.x, (int)t, wave, 0);
+                    redo[2 * (size_t)slot + 1] = make_int4((int)r0, (int)p0, 0, 0);
+                }
+            }
+            slot = __builtin_amdgcn_readfirstlane(slot);
+            if (slot >= redo_cap) {                                  // (never, in practice) the rows this wave may have lost
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn)
+                    if (qi[tn] < n) row_fail[qi[tn]] = 1;
+                if (offdiag && my_j < n) row_fail[my_j] = 1;
+            }
+        }
+    };
+    const int64_t n_tiles = (int64_t)(item.z - item.y);
+    auto m_tile = [=](int64_t t) { return (int64_t)(item.y + t) * TILE; };
+    if constexpr (NCH > 0) tile_pipeline_bf16_breg<NCH>(e, kp, e, q0, n_tiles, m_tile, As, epilogue, dim);
+    else tile_pipeline_bf16<false>(e, kp, e, dim, q0, n_tiles, m_tile, As, Bs, epilogue);
+    if (lane == 0) {
+        coff[n_tiles] = (int32_t)(cpos >> 3);
+        row_cnt[wid] = (int32_t)(min(rpos, rbytes) >> 3);
+    }
+}
+
+// the tiles of the redo list, again: only the recorded wave writes, and only what did not fit its streams
+__global__ __launch_bounds__(256, 2) void topk_stream_redo_kernel(
+    const float *__restrict__ e, int64_t n, int kp, int dim, const float *__restrict__ thr, const int4 *__restrict__ items, int rcap, int ccap,
+    uint8_t *__restrict__ row_fail, const float *__restrict__ tol_ptr, const int32_t *__restrict__ redo_cnt, const int4 *__restrict__ redo,
+    int redo_cap, uint4 *__restrict__ ovf_pool, int32_t *__restrict__ ovf_alloc, int32_t *__restrict__ ovf_len, int ovf_chunks) {
+    __shared__ __attribute__((aligned(16))) float As[2 * TILE * LDS_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[2 * TILE * LDS_LD];
+    const int n_redo = min(*redo_cnt, redo_cap);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int half = lane >> 5, l32 = lane & 31;
+    const uint32_t rbytes = 8u * (uint32_t)rcap, cbytes = 8u * (uint32_t)ccap;
+    const float tol = *tol_ptr;
+    OvfState ovf{ovf_pool, ovf_alloc, ovf_len, row_fail, (uint32_t)ovf_chunks, 0xFFFFFFFFu, (uint32_t)kOvfChunk};
+    const int jl0 = wm * 64 + 4 * half;
+    const int my_jl = jl0 + (l32 >> 4) * 32 + (l32 & 3) + 8 * ((l32 & 15) >> 2);
+    for (int idx = blockIdx.x; idx < n_redo; idx += gridDim.x) {
+        const int4 ent = redo[2 * (size_t)idx], pos = redo[2 * (size_t)idx + 1];
+        const int4 item = items[ent.x];
+        const int qt = item.x, ct = item.y + ent.y;
+        const int64_t q0 = (int64_t)qt * TILE, c0 = (int64_t)ct * TILE;
+        float th[2];
+        uint32_t qidx[2];
+        int64_t qi[2];
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            qi[tn] = q0 + wn * 64 + tn * 32 + l32;
+            th[tn] = qi[tn] < n ? thr[qi[tn]] - tol : INFINITY;
+            qidx[tn] = (uint32_t)qi[tn];
+        }
+        const int64_t my_j = c0 + my_jl;
+        const float my_tc = (ct != qt && my_j < n) ? thr[my_j] - tol : INFINITY;
+        tile_pipeline_bf16<false>(e, kp, e, dim, q0, 1, [=](int64_t) { return c0; }, As, Bs, [&](int64_t, f32x16 (&acc)[2][2]) {
+            if (wave != ent.z) return;
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+#pragma unroll
+                    for (int tn = 0; tn < 2; ++tn)
+                        if (qi[tn] >= n) acc[tm][tn][r] = -INFINITY;
+            if (c0 + TILE <= n) stream_ovf_tile<true>(acc, (int)c0, jl0, (int)n, th, qidx, my_tc, lane, rbytes, cbytes, (uint32_t)pos.x, (uint32_t)pos.y, ovf);
+            else stream_ovf_tile<false>(acc, (int)c0, jl0, (int)n, th, qidx, my_tc, lane, rbytes, cbytes, (uint32_t)pos.x, (uint32_t)pos.y, ovf);
+        });
+        __syncthreads();                                             // the LDS buffers are staged again by the next entry
+    }
+    if (lane == 0 && ovf.chunk < ovf.cap_chunks) ovf_len[ovf.chunk] = (int32_t)ovf.used;
+}
+
 // ---- stream form of the symmetric search (bf16 sweep): the records of one target tile -> its 128 rows' compact lists -----------
-// topk_stream_sym_kernel (sim_rank.hip) leaves, per wave of every work item, a stream of query-side records (targets: the 128
+// topk_stream_sym_kernel leaves, per wave of every work item, a stream of query-side records (targets: the 128
 // rows of the item's query tile) and a stream of candidate-side records whose position at every candidate-tile boundary is
 // known (col_off).  One workgroup per target tile tau collects its records: the whole query-side streams of the items (tau, c),
 // c >= tau / L, and from every item (qt <= tau, c = tau / L) the slice of the candidate-side streams written while it was on
@@ -1541,7 +1922,7 @@ static int redo_failed_rows(const float *qp, int kp, const float *cp, int64_t nc
         const int cnt_pad = (cnt + 127) / 128 * 128;
         gather_rows_list_kernel<<<(unsigned)std::min<int64_t>(oea::ceil_div((int64_t)cnt_pad * (kp / 4), 256), 4096), 256, 0, st>>>(
             qp, kp, fail_rows + b0, cnt, cnt_pad, gq);
-        oea::sim_inner_store_packed(gq, cnt, cp, nc, kp, dim, strip, ld, st);
+        sim_inner_store_packed(gq, cnt, cp, nc, kp, dim, strip, ld, st);
         launch_select(strip, cnt, nc, ld, k, id_map, sel, st);
         scatter_selected_kernel<<<(unsigned)std::min<int64_t>(oea::ceil_div((int64_t)cnt * k, 256), 8192), 256, 0, st>>>(
             sel, k, fail_rows + b0, cnt, out);
@@ -1550,10 +1931,52 @@ static int redo_failed_rows(const float *qp, int kp, const float *cp, int64_t nc
     return OEA_OK;
 }
 
+// ---- launches of the sweep kernels -------------------------------------------------------------------------------------------
+// The fixed operand of a bf16 sweep in registers (tile_pipeline_bf16_breg: the other operand's stages alone travel through LDS,
+// nothing is re-sent per chunk) where Kp is 96 or 128, i.e. 64 < dim <= 128: the kernels fit (20 B of scratch) -- 11.3 -> 10.5 ms
+// at 100,000^2 x 100.  OEA_TOPK_STREAM_NCH=0: both operands through LDS.
+static bool sweep_breg() {
+    static const bool on = [] { const char *e = getenv("OEA_TOPK_STREAM_NCH"); return e ? atoi(e) != 0 : true; }();
+    return on;
+}
+
+// list form: the survivors of the threshold sweep of a block of query rows into per-query list segments (topk_append_kernel),
+// `chunks` candidate chunks as planned by plan_lists.  tol_dev != NULL: qp / cp are the bf16 split rows, tol_dev[0] the bound.
+static void launch_append(const float *qp, int64_t nq, const float *cp, int64_t nc, int kp, int dim, const float *thr, int cap, int chunks,
+                          float *list_vals, int32_t *list_cols, int32_t *counts, int32_t *spill_cnt, uint2 *spill, int sp_cap,
+                          const float *tol_dev, hipStream_t st) {
+    const int tpc = (int)ceil_div(ceil_div(nc, TILE), chunks);
+    const dim3 grid((unsigned)ceil_div(nq, TILE), (unsigned)chunks);
+#define OEA_APPEND_LAUNCH(...)                                                                                                              \
+    topk_append_kernel<__VA_ARGS__><<<grid, 256, 0, st>>>(qp, nq, kp, cp, nc, kp, dim, thr, tpc, cap, list_vals, list_cols, counts, spill_cnt, \
+                                                          spill, sp_cap, tol_dev)
+    if (!tol_dev) OEA_APPEND_LAUNCH(false);
+    else if (sweep_breg() && kp == 128) OEA_APPEND_LAUNCH(true, 4);
+    else if (sweep_breg() && kp == 96) OEA_APPEND_LAUNCH(true, 3);
+    else OEA_APPEND_LAUNCH(true, 0);
+#undef OEA_APPEND_LAUNCH
+}
+
+// stream form: the symmetric sweep over the work items on the bf16 split rows ep, then the tiles of its redo list again
+static void launch_stream_sweep(const float *ep, int64_t n, int kp, int dim, const float *thr, const int4 *items, int n_items,
+                                uint2 *row_streams, int rcap, uint2 *col_streams, int ccap, int32_t *row_cnt, int32_t *col_off, int lp1,
+                                uint8_t *row_fail, const float *tol_dev, uint4 *ovf_pool, int32_t *ovf_alloc, int32_t *ovf_len,
+                                int ovf_chunks, int32_t *redo_cnt, int4 *redo, int redo_cap, hipStream_t st) {
+#define OEA_STREAM_LAUNCH(N)                                                                                                          \
+    topk_stream_sym_kernel<N><<<(unsigned)n_items, 256, 0, st>>>(ep, n, kp, dim, thr, items, row_streams, rcap, col_streams, ccap, row_cnt, \
+                                                                 col_off, lp1, row_fail, tol_dev, redo_cnt, redo, redo_cap)
+    if (sweep_breg() && kp == 128) OEA_STREAM_LAUNCH(4);
+    else if (sweep_breg() && kp == 96) OEA_STREAM_LAUNCH(3);
+    else OEA_STREAM_LAUNCH(0);
+#undef OEA_STREAM_LAUNCH
+    topk_stream_redo_kernel<<<2048, 256, 0, st>>>(ep, n, kp, dim, thr, items, rcap, ccap, row_fail, tol_dev, redo_cnt, redo, redo_cap, ovf_pool,
+                                                  ovf_alloc, ovf_len, ovf_chunks);
+}
+
 }  // namespace
 
 namespace oea {
-// shared with the one-sweep CSLS means (sim_rank.hip)
+// shared with the one-sweep CSLS means (csls_means.hip; declared in sim_tiles.h)
 int kth_value(const float *strip, int64_t rows, int sample, int r, float *thr, hipStream_t st) {
     const unsigned grid = (unsigned)ceil_div(rows, 4);
     if (sample == 1024) kth_value_kernel<16><<<grid, 256, 0, st>>>(strip, rows, sample, r, thr);
@@ -1683,13 +2106,14 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
     if (rows_per < 128) rows_per = nq;
     float *strip = static_cast<float *>(workspace);
     hipStream_t st = oea::as_stream(stream);
-    float *qp = nullptr, *cp = nullptr;             // both operands packed once for all strips (sim_rank.hip)
-    int kp = 0;
+    PackedOp pq, pc;                                // both operands packed once for all strips (slots 0 and 1)
     {
-        int rc = oea::pack_rows(0, q, nq, ldq, dim, st, &qp, &kp);
-        if (rc == OEA_OK) rc = oea::pack_rows(1, c, nc, ldc, dim, st, &cp, &kp);
+        int rc = pack_operand(0, q, nq, ldq, dim, st, &pq);
+        if (rc == OEA_OK) rc = pack_operand(1, c, nc, ldc, dim, st, &pc);
         if (rc != OEA_OK) return rc;
     }
+    const float *qp = pq.p, *cp = pc.p;
+    const int kp = pq.kp;
     static const bool lists_on = [] { const char *e = getenv("OEA_TOPK_LISTS"); return !(e && e[0] == '0'); }();
     const bool same = q == c && nq == nc && ldq == ldc;
     static const bool bf16_sweep = [] { const char *e = getenv("OEA_TOPK_BF16"); return !(e && e[0] == '0'); }();
@@ -1700,7 +2124,10 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         int32_t *fail_rows = reinterpret_cast<int32_t *>(w + sp.off_fail);
         int32_t *n_fail = reinterpret_cast<int32_t *>(w + sp.off_nfail);
         float *tol_dev = reinterpret_cast<float *>(w + sp.off_nfail + 64);
-        int32_t *items_dev = reinterpret_cast<int32_t *>(w + sp.off_items);
+        int4 *items_dev = reinterpret_cast<int4 *>(w + sp.off_items);
+        uint2 *rstream = reinterpret_cast<uint2 *>(w + sp.off_rstream), *cstream = reinterpret_cast<uint2 *>(w + sp.off_cstream);
+        uint4 *ovf_pool = reinterpret_cast<uint4 *>(w + sp.off_ovf);
+        int4 *redo = reinterpret_cast<int4 *>(w + sp.off_redo);
         int32_t *row_cnt = reinterpret_cast<int32_t *>(w + sp.off_rcnt);
         int32_t *col_off = reinterpret_cast<int32_t *>(w + sp.off_coff);
         int32_t *list_cnt = reinterpret_cast<int32_t *>(w + sp.off_lcnt);
@@ -1708,33 +2135,36 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         float *sstrip = reinterpret_cast<float *>(w + sp.off_strip);
         uint2 *lists = reinterpret_cast<uint2 *>(w + sp.off_lists);
         OEA_REQUIRE(kp <= 4096, "dim <= 4096 on the list path");
-        sym_items_kernel<<<(unsigned)oea::ceil_div((int64_t)sp.groups * sp.T, 256), 256, 0, st>>>(sp.T, sp.L, sp.groups,
-                                                                                              reinterpret_cast<int4 *>(items_dev));
+        sym_items_kernel<<<(unsigned)oea::ceil_div((int64_t)sp.groups * sp.T, 256), 256, 0, st>>>(sp.T, sp.L, sp.groups, items_dev);
         // the sample strip on the bf16 split as well (OEA_TOPK_BF16_STRIP=0: fp32): thresholds are estimates, see sample_strip_bf16_pack
         static const bool bf16_strip = [] { const char *e = getenv("OEA_TOPK_BF16_STRIP"); return !(e && e[0] == '0'); }();
         int rc = OEA_OK;
         if (bf16_strip) {
             const float *qs = nullptr, *ss = nullptr;
             int kps2 = 0;
-            rc = oea::sample_strip_bf16_pack(c, nc, ldc, c, kSample, ldc * (int)sp.stride, dim, st, &qs, &ss, &kps2);
+            rc = sample_strip_bf16_pack(c, nc, ldc, c, kSample, ldc * (int)sp.stride, dim, st, &qs, &ss, &kps2);
             if (rc != OEA_OK) return rc;
-            oea::sample_strip_bf16_launch(qs, nq, ss, kSample, kps2, dim, sstrip, st);
+            sample_strip_bf16_launch(qs, nq, ss, kSample, kps2, dim, sstrip, st);
         } else {
-            float *smp = nullptr;
-            int kps = 0;
-            rc = oea::pack_rows(2, c, kSample, ldc * (int)sp.stride, dim, st, &smp, &kps);
+            PackedOp smp;
+            rc = pack_operand(2, c, kSample, ldc * (int)sp.stride, dim, st, &smp);
             if (rc != OEA_OK) return rc;
-            oea::sim_inner_store_packed(qp, nq, smp, kSample, kp, dim, sstrip, kSample, st);
+            sim_inner_store_packed(qp, nq, smp.p, kSample, kp, dim, sstrip, kSample, st);
         }
         kth_value_kernel<kSample / 64><<<(unsigned)oea::ceil_div(nq, 4), 256, 0, st>>>(sstrip, nq, kSample, sp.r, thr);
         int32_t *ovf_alloc = reinterpret_cast<int32_t *>(w + sp.off_nfail + 128);
         int32_t *ovf_len = reinterpret_cast<int32_t *>(w + sp.off_ovflen);
         OEA_CHECK_HIP(hipMemsetAsync(n_fail, 0, 256, st));           // failure count, tolerance block, overflow chunk count
         OEA_CHECK_HIP(hipMemsetAsync(row_fail, 0, (size_t)nq, st));
-        rc = oea::topk_stream_sym_bf16(c, nc, ldc, dim, thr, items_dev, sp.n_items, w + sp.off_rstream, sp.rcap, w + sp.off_cstream, sp.ccap,
-                                       row_cnt, col_off, sp.L + 1, row_fail, tol_dev, w + sp.off_ovf, ovf_alloc, ovf_len, sp.ovf_chunks,
-                                       ovf_alloc + 1, w + sp.off_redo, sp.redo_cap, st, bf16_strip);
+        // the rows split into slot 3 (where sample_strip_bf16_pack has left them already), the bound on |v~ - v| into tol_dev[0]
+        PackedOp es;
+        int64_t n_pad_unused = 0;
+        rc = bf16_strip ? reserve_operand(3, nc, dim, st, &es, &n_pad_unused) : pack_operand_bf16(3, c, nc, ldc, dim, st, &es);
         if (rc != OEA_OK) return rc;
+        OEA_CHECK_HIP(hipMemsetAsync(tol_dev, 0, 8, st));
+        bf16_tol_bound(c, nc, ldc, nullptr, 0, 0, dim, false, tol_dev, st);
+        launch_stream_sweep(es.p, nc, es.kp, dim, thr, items_dev, sp.n_items, rstream, sp.rcap, cstream, sp.ccap, row_cnt, col_off, sp.L + 1,
+                            row_fail, tol_dev, ovf_pool, ovf_alloc, ovf_len, sp.ovf_chunks, ovf_alloc + 1, redo, sp.redo_cap, st);
         const size_t bucket_lds = sizeof(uint32_t) * (2 * (64 + 4 * (size_t)sp.T) + 2) + 8 * (size_t)kBucketFlight * kBucketThreads;
         static const hipError_t bucket_attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_bucket_kernel),
                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 1024 * (4 + kBucketFlight * kBucketThreads / 1024) + 1024);
@@ -1743,10 +2173,9 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         OEA_CHECK_HIP(hipMemsetAsync(list_cnt, 0, sizeof(int32_t) * (size_t)sp.T * 128, st));
         const int parts = std::max(1, std::min(16, (int)oea::ceil_div(1024, sp.T)));
         topk_bucket_kernel<<<(unsigned)(sp.T * parts), kBucketThreads, bucket_lds, st>>>(
-            sp.T, sp.L, sp.groups, nq, reinterpret_cast<const uint2 *>(w + sp.off_rstream), sp.rcap, row_cnt,
-            reinterpret_cast<const uint2 *>(w + sp.off_cstream), sp.ccap, col_off, sp.L + 1, lists, sp.row_cap, list_cnt, row_fail, parts);
-        topk_overflow_kernel<<<1024, 256, 0, st>>>(reinterpret_cast<const uint4 *>(w + sp.off_ovf), ovf_alloc, ovf_len, sp.ovf_chunks, lists,
-                                                   sp.row_cap, list_cnt, row_fail);
+            sp.T, sp.L, sp.groups, nq, rstream, sp.rcap, row_cnt, cstream, sp.ccap, col_off, sp.L + 1, lists, sp.row_cap, list_cnt, row_fail,
+            parts);
+        topk_overflow_kernel<<<1024, 256, 0, st>>>(ovf_pool, ovf_alloc, ovf_len, sp.ovf_chunks, lists, sp.row_cap, list_cnt, row_fail);
         static const bool dbg_ovf = getenv("OEA_TOPK_DEBUG") != nullptr;
         if (dbg_ovf) {
             int32_t na = 0;
@@ -1759,9 +2188,9 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         list_select_kernel<<<(unsigned)nq, SEL_THREADS, select_lds_bytes(nc), st>>>(
             nullptr, nullptr, nullptr, thr, 0, 0, nc, k, id_map, out_idx, fail_rows, n_fail, nullptr, nullptr,
             select_stop(), c, ldc, dim, tol_dev, lists, list_cnt, sp.row_cap, row_fail);
-        rc = redo_failed_rows(qp, kp, cp, nc, dim, k, id_map, out_idx, fail_rows, n_fail, w + sp.off_rstream, 2 * sp.stream_bytes, sp.ld, st);
+        rc = redo_failed_rows(qp, kp, cp, nc, dim, k, id_map, out_idx, fail_rows, n_fail, rstream, 2 * sp.stream_bytes, sp.ld, st);
         if (rc != OEA_OK) return rc;
-        rc = oea::release_packed_rows(st);
+        rc = release_packed(st);
         if (rc != OEA_OK) return rc;
         OEA_CHECK_HIP(hipGetLastError());
         return OEA_OK;
@@ -1777,7 +2206,7 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         int32_t *list_cols = reinterpret_cast<int32_t *>(w + lp.off_lists + lp.cols_off);
         float *sstrip = reinterpret_cast<float *>(w + lp.off_strip);
         int32_t *spill_cnt = reinterpret_cast<int32_t *>(w + lp.off_spcnt);
-        void *spill = w + lp.off_spill;
+        uint2 *spill = reinterpret_cast<uint2 *>(w + lp.off_spill);
         OEA_REQUIRE(kp <= 4096, "dim <= 4096 on the list path");
         // the sweep on the bf16 hi / lo split of both tables (3 / 16 of the fp32 matrix time; OEA_TOPK_BF16=0: the exact fp32 sweep):
         // approximate list values, the select decides the neighbourhood of the k-th value with exact chains -- same sets; the sample
@@ -1787,49 +2216,56 @@ int oea_topk_inner(const float *q, int64_t nq, int32_t ldq, const float *c, int6
         float *tol_dev = reinterpret_cast<float *>(w + lp.off_nfail + 64);
         const float *qs = nullptr, *cs = nullptr, *ss = nullptr;
         int kps2 = 0, rc = OEA_OK;
-        float *sp = nullptr;
-        int kps = 0;
-        if (strip16) rc = oea::sample_strip_bf16_pack(q, nq, ldq, c, kSample, ldc * (int)lp.stride, dim, st, &qs, &ss, &kps2);
-        else rc = oea::pack_rows(2, c, kSample, ldc * (int)lp.stride, dim, st, &sp, &kps);   // every stride-th candidate row
+        PackedOp smp;
+        if (strip16) rc = sample_strip_bf16_pack(q, nq, ldq, c, kSample, ldc * (int)lp.stride, dim, st, &qs, &ss, &kps2);
+        else rc = pack_operand(2, c, kSample, ldc * (int)lp.stride, dim, st, &smp);   // every stride-th candidate row
         if (rc != OEA_OK) return rc;
         if (bf16_sweep) {
-            rc = oea::topk_append_bf16_prepare(q, nq, ldq, c, nc, ldc, dim, tol_dev, st, &qs, &cs, &kps2, strip16);
+            // both tables split (slots 3 / 4; under strip16 the query rows are in slot 3 already), the bound on |v~ - v| into
+            // tol_dev[0] (the tables' largest row norms in tol_dev[1], [2])
+            PackedOp sq, sc;
+            int64_t n_pad_unused = 0;
+            rc = strip16 ? reserve_operand(3, nq, dim, st, &sq, &n_pad_unused) : pack_operand_bf16(3, q, nq, ldq, dim, st, &sq);
+            if (rc == OEA_OK) rc = pack_operand_bf16(4, c, nc, ldc, dim, st, &sc);
             if (rc != OEA_OK) return rc;
+            OEA_CHECK_HIP(hipMemsetAsync(tol_dev, 0, 16, st));
+            bf16_tol_bound(q, nq, ldq, c, nc, ldc, dim, false, tol_dev, st);
+            qs = sq.p; cs = sc.p; kps2 = sq.kp;
         }
         for (int64_t r0 = 0; r0 < nq; r0 += lp.rows_per) {
             const int64_t rows = std::min<int64_t>(lp.rows_per, nq - r0);
-            if (strip16) oea::sample_strip_bf16_launch(qs + r0 * kps2, rows, ss, kSample, kps2, dim, sstrip, st);
-            else oea::sim_inner_store_packed(qp + r0 * kp, rows, sp, kSample, kp, dim, sstrip, kSample, st);
+            if (strip16) sample_strip_bf16_launch(qs + r0 * kps2, rows, ss, kSample, kps2, dim, sstrip, st);
+            else sim_inner_store_packed(qp + r0 * kp, rows, smp.p, kSample, kp, dim, sstrip, kSample, st);
             kth_value_kernel<kSample / 64><<<(unsigned)oea::ceil_div(rows, 4), 256, 0, st>>>(sstrip, rows, kSample, lp.r, thr);
             OEA_CHECK_HIP(hipMemsetAsync(n_fail, 0, sizeof(int32_t), st));
             // the chunk count (hence the segment layout) is the one planned for a full pass: a short last pass reuses it
             OEA_CHECK_HIP(hipMemsetAsync(spill_cnt, 0, sizeof(int32_t) * (size_t)rows, st));
             if (bf16_sweep)
-                oea::topk_append_bf16_launch(qs + r0 * kps2, rows, cs, nc, kps2, dim, thr, lp.cap, lp.chunks, list_vals, list_cols, counts,
-                                             spill_cnt, spill, kSpillCap, tol_dev, st);
+                launch_append(qs + r0 * kps2, rows, cs, nc, kps2, dim, thr, lp.cap, lp.chunks, list_vals, list_cols, counts, spill_cnt, spill,
+                              kSpillCap, tol_dev, st);
             else
-                oea::topk_append_packed(qp + r0 * kp, rows, cp, nc, kp, dim, thr, lp.cap, lp.chunks, list_vals, list_cols, counts, spill_cnt,
-                                        spill, kSpillCap, st);
+                launch_append(qp + r0 * kp, rows, cp, nc, kp, dim, thr, lp.cap, lp.chunks, list_vals, list_cols, counts, spill_cnt, spill,
+                              kSpillCap, nullptr, st);
             list_select_kernel<<<(unsigned)rows, SEL_THREADS, select_lds_bytes(nc), st>>>(
                 list_vals, list_cols, counts, thr, lp.nseg, lp.cap, nc, k, id_map, out_idx + r0 * (int64_t)k, fail_rows, n_fail,
-                spill_cnt, static_cast<const uint2 *>(spill), select_stop(), bf16_sweep ? c : nullptr, ldc, dim,
+                spill_cnt, spill, select_stop(), bf16_sweep ? c : nullptr, ldc, dim,
                 bf16_sweep ? tol_dev : nullptr, nullptr, nullptr, 0, nullptr, bf16_sweep ? q + r0 * (int64_t)ldq : nullptr, ldq);
             // rows the select gave up on: through the strip path, in batches, inside the (now dead) list storage
             rc = redo_failed_rows(qp + r0 * kp, kp, cp, nc, dim, k, id_map, out_idx + r0 * (int64_t)k, fail_rows, n_fail, list_vals,
                                   2 * lp.cols_off, lp.ld, st);
             if (rc != OEA_OK) return rc;
         }
-        rc = oea::release_packed_rows(st);
+        rc = release_packed(st);
         if (rc != OEA_OK) return rc;
         OEA_CHECK_HIP(hipGetLastError());
         return OEA_OK;
     }
     for (int64_t r0 = 0; r0 < nq; r0 += rows_per) {              // r0 is a multiple of 128: strips start on tile rows
         const int64_t rows = std::min<int64_t>(rows_per, nq - r0);
-        oea::sim_inner_store_packed(qp + r0 * kp, rows, cp, nc, kp, dim, strip, ld, st);
+        sim_inner_store_packed(qp + r0 * kp, rows, cp, nc, kp, dim, strip, ld, st);
         launch_select(strip, rows, nc, ld, k, id_map, out_idx + r0 * (int64_t)k, st);
     }
-    const int rc = oea::release_packed_rows(st);
+    const int rc = release_packed(st);
     if (rc != OEA_OK) return rc;
     OEA_CHECK_HIP(hipGetLastError());
     return OEA_OK;

@@ -20,7 +20,7 @@ torch = pytest.importorskip("torch")
 F32 = np.float32
 U32 = 2.0 ** -24                      # fp32 unit roundoff
 U64 = 2.0 ** -53                      # fp64 unit roundoff
-K_AMB, K_TOP = 2048, 4096             # sim_rank.hip kGridAmb / kGridTop: the capacities of a row's two candidate lists
+K_AMB, K_TOP = 2048, 4096             # l1_grid.hip kGridAmb / kGridTop: the capacities of a row's two candidate lists
 SENT = 7.0                            # strip sentinel: a strip holds -G <= -0.0, never a positive value
 
 
