@@ -255,7 +255,7 @@ __global__ __launch_bounds__(64 * kGradWaves) void char_grad_kernel(const float 
     }
 }
 
-// back through the normalisation and one optimiser step on a row held as columns 2 l, 2 l + 1 (apply_one_row of triple_step.hip)
+// back through the normalisation and one optimiser step on a row held as columns 2 l, 2 l + 1 (apply_one_row of step_rows.h)
 __device__ __forceinline__ float2 through_l2n(float2 r, float2 g, int on) {
     if (!on) return g;
     const float ss = dot2(r, r);
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(64 * kWaves) void joint_kernel(float *ent, float *e
         if (adagrad) { aa = load2_acc(ent_acc + e * ld, dim, lane); ba = load2_acc(ce_acc + e * ld, dim, lane); }
         for (int s = 0; s < steps; ++s) {
             // three wave sums a step: the two norms and the cosine.  The gradient w.r.t. ya is -m yb, so the y . g of the way back
-            // through the normalisation is -m cs (and 0 for a clamped row, as apply_one_row of triple_step.hip has it)
+            // through the normalisation is -m cs (and 0 for a clamped row, as apply_one_row of step_rows.h has it)
             float ia = 1.f, ib = 1.f, pa = 0.f, pb = 0.f;
             if (l2n) {
                 const float sa = dot2(a, a), sb = dot2(b, b);

@@ -242,7 +242,7 @@ int oea_comm_profile_end(oea_comm_t c, double *phase_ms, int32_t *steps) {
 
 }  // extern "C"
 
-// boundary `i` (0 .. OEA_COMM_PHASES) of the current step of oea_triple_epoch_range_comm (triple_step.hip)
+// boundary `i` (0 .. OEA_COMM_PHASES) of the current step of oea_triple_epoch_range_comm (step_epochs.hip)
 namespace oea {
 int comm_phase_mark(oea_comm_t c, hipStream_t st) {
     if (!c || !c->profiling) return OEA_OK;

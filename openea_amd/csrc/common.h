@@ -170,7 +170,7 @@ __device__ __forceinline__ void grad_add_raw(float *p, float q) { unsafeAtomicAd
 #endif
 
 // where a step that rides on the engine adds its rows: the entity rows, copy 0 of the relation rows, and their touched flags inside
-// a step workspace (triple_step.hip, the one place that knows the order of the regions)
+// a step workspace (defined in triple_step.hip on step_rows.h:ws_layout, the one place that knows the order of the regions)
 void step_scratch_rows(void *workspace, int64_t n_ent, int64_t n_rel, int32_t ld, grad_t **ent_grad, flag_t **ent_touched,
                        grad_t **rel_grad, flag_t **rel_touched);
 

@@ -1,4 +1,5 @@
-// step_plan.h -- the "gathered sum" plan of a translational epoch (round 6), shared by step_plan.hip (build) and triple_step.hip (use).
+// step_plan.h -- the "gathered sum" plan of a translational epoch (round 6), shared by step_plan.hip (build), triple_step.hip (use: the
+// planned step's kernels) and step_epochs.hip (oea_triple_epoch_range, which has it built and hands it to every step).
 //
 // Why: device-scope fp32 atomics on gfx950 execute MEMORY-SIDE (every request leaves the XCD's L2: TCC_EA0_ATOMIC == TCC_ATOMIC,
 // profiles/r06_step_wave_pmc_atomics.csv) at ~20 G requests of 64 B per second -- 24 of triple_wave's 54 us at the 100K shape, most

@@ -36,7 +36,7 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.CsrSplit) == 80           # 4 pointers + 3 int32 (+ pad) + 2 pointers + int64 + pointer of oea_csr_split
     assert C.sizeof(_lib.AttnGraph) == 30 * 8      # 13 pointers + 17 int64 of oea_attn_graph
     assert C.sizeof(_lib.Epoch) == 184             # oea_epoch: 16 pointers + 3 x 8-byte integers + 5 x int32, three of them padded to 8
-                                                   # (the static_assert in csrc/triple_step.hip holds the C side to the same number)
+                                                   # (the static_assert in csrc/step_epochs.hip holds the C side to the same number)
 
 
 def test_host_side_planners_of_the_library():

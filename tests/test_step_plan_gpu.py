@@ -41,7 +41,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HUB_ENTRIES = 8                  # csrc/step_plan.h: kPlanHubEntries
 NEAR = 1e-5                      # |float64 score - margin| <= NEAR: the triple's rows are left out of the step's row comparison
-PLAN_BLOCKS, SCAN_BLOCKS, MAX_PARTIALS = 8192, 4096, 4096      # csrc/triple_step.hip:launch_step's caps, kMaxBlocks
+PLAN_BLOCKS, SCAN_BLOCKS, MAX_PARTIALS = 8192, 4096, 4096      # csrc/triple_step.hip:launch_step's caps, csrc/step_rows.h:kMaxBlocks
 
 
 @pytest.fixture(scope="module")
