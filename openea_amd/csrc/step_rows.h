@@ -49,10 +49,10 @@ struct StepWs {
     flag_t *ent_touched, *rel_touched;  // 1 = row received gradient (same type as the gradients: one SUM all-reduce covers both)
     grad_t *nrm_grad, *nrm_extra;       // TransH normal vectors: copy 0 / copies 1.. (same shapes as the relation scratch)
     flag_t *nrm_touched;
-    double *partials;                   // [kMaxBlocks]
+    double *partials;                   // [kMaxBlocks]; the planned step's partials past kMaxBlocks lie BEFORE it (plan_partial)
     // layout: [ent_grad | rel_grad (copy 0) | nrm_grad (copy 0) | ent_touched | rel_touched | nrm_touched] is the
     // contiguous prefix that data-parallel ranks all-reduce (the extra copies are folded into copy 0 first);
-    // [rel_extra | nrm_extra | partials] follow.
+    // [rel_extra | nrm_extra | planned partials kMaxBlocks .. kMaxPlanPartials - 1 | partials] follow.
     __device__ __forceinline__ grad_t *rel_copy(int64_t c) const {
         return c == 0 ? rel_grad : rel_extra + (c - 1) * rel_copy_stride;
     }
@@ -61,6 +61,14 @@ struct StepWs {
     }
 };
 constexpr int kMaxBlocks = 4096;
+// The planned step (triple_step.hip: wave_geometry) runs one 4-wave workgroup per 4 positives and leaves up to kMaxPlanPartials
+// partials.  The workspace ends with the kMaxBlocks partials every step has; everything before them is zero between steps (the
+// scratch, the flags -- tests/test_step_plan_gpu.py holds a step to it), so the planned step's partials past kMaxBlocks, which lie
+// before them, are cleared by the block that adds them up (add_loss_partials_block).
+constexpr int kMaxPlanPartials = 8192;
+__host__ __device__ __forceinline__ double *plan_partial(const StepWs &ws, int b) {
+    return ws.partials + (b < kMaxBlocks ? b : b - kMaxPlanPartials);
+}
 // Relation rows are few (a few hundred) and shared by the whole batch: with one scratch row per
 // relation the hottest relation took ~750 same-address atomics per step (19 of 45 us, measured).
 // The relation scratch is therefore replicated kRelCopies times; a work item adds into copy
@@ -79,6 +87,8 @@ static size_t ws_layout(int64_t n_ent, int64_t n_rel, int32_t ld, void *base, St
     flag_t *nt = (flag_t *)take(sizeof(flag_t) * (size_t)n_rel);
     grad_t *rx = (grad_t *)take(sizeof(grad_t) * (size_t)n_rel * ld * (kRelCopies - 1));
     grad_t *nx = (grad_t *)take(sizeof(grad_t) * (size_t)n_rel * ld * (kRelCopies - 1));
+    static_assert(sizeof(double) * (kMaxPlanPartials - kMaxBlocks) % 256 == 0, "plan_partial: the two partial ranges are contiguous");
+    (void)take(sizeof(double) * (kMaxPlanPartials - kMaxBlocks));
     double *pp = (double *)take(sizeof(double) * kMaxBlocks);
     if (ws) {
         ws->rel_copy_stride = n_rel * (int64_t)ld; ws->ent_grad = eg; ws->rel_grad = rg; ws->rel_extra = rx;

@@ -471,8 +471,10 @@ __device__ __forceinline__ void wave_normalize(Row<64, IT> &r) {
 // ascending order of relation id, so a workgroup's waves nearly always hold one relation -- and the relation rows of a workgroup are
 // summed in LDS before the atomics.  Everything else is indexed by the positive's batch index as before.  nullptr: slot q handles
 // positive q and every wave issues its own relation row (OEA_STEP_REL_ORDER=0).
-template <int IT, int L1, int KT, bool PLAN>
-__global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void triple_wave(
+// WPB: waves per workgroup of a PLAN launch (launch_wave: 4, or 8 under OEA_STEP_WAVE_BLOCK=512) -- the rows of the relation sum in
+// LDS; without a plan the workgroup is whatever launch_grouped gives it and nothing is summed.
+template <int IT, int L1, int KT, bool PLAN, int WPB = 8>
+__global__ __launch_bounds__(PLAN ? WPB * 64 : 512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void triple_wave(
     const float *__restrict__ ent, const float *__restrict__ rel, int ld, const int32_t *__restrict__ pos,
     int64_t n_pos, const int32_t *__restrict__ neg, int k, oea_step_cfg cfg, StepWs ws, int dbg, float *__restrict__ contrib,
     const uint32_t *__restrict__ pflags, const uint32_t *__restrict__ order) {
@@ -480,7 +482,7 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
     if (KT > 0) k = KT;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wpb = blockDim.x >> 6;                                          // 8 (ld <= 128) or 4 waves: launch_step's groups per block
+    const int wpb = blockDim.x >> 6;                                          // wave_geometry's block: 4 or 8 waves (PLAN: WPB)
     const int64_t nw = (int64_t)gridDim.x * wpb;
     const int row_b = ld * 4, row_g = ld << kGradShift;                       // bytes per table row / scratch row
     // dbg (OEA_STEP_WAVE_DBG, experiments only): bit 0 = an empty resource for the scratch (every atomic is issued and dropped), bit 1 =
@@ -756,10 +758,10 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
             // in wave order that holds a relation adds the rows of the later waves that hold it too, in wave order (equal relations
             // need not be adjacent), and issues ONE row of atomics and ONE flag for the group, into the scratch copy of its own
             // positive.  Waves past the end, waves inside both margins and waves that scored independent triples (their atomics
-            // are done) bring "no row" (-1).  Any number of waves per workgroup: under OEA_STEP_WAVE_BLOCK=256 a workgroup is 4
-            // waves that take two slots each, and every pass of this loop sums its own 4 rows.
-            __shared__ float s_row[8][IT][64];
-            __shared__ int s_rel[8];
+            // are done) bring "no row" (-1).  Any number of waves per workgroup: 4 with one slot each (wave_geometry), 4 that take
+            // two slots each under OEA_STEP_WAVE_BLOCK=256 (every pass of this loop sums its own 4 rows), 8 under =512.
+            __shared__ float s_row[WPB][IT][64];
+            __shared__ int s_rel[WPB];
             // this lane's byte offset inside a 64-float fragment, taken from the register the row loads use and made opaque: the
             // LDS addresses are formed here, not hoisted out of the loop into registers the scoring code needs (measured: 9 spilled)
             int lb = v4;
@@ -775,10 +777,10 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
                 const int held = lb < wpb * 4 ? *at(&s_rel[0]) : -1;         // lane w: the relation wave w holds
                 bool first = true;
 #pragma unroll
-                for (int w = 0; w < 8; ++w) first = first && !(w < wv && __builtin_amdgcn_readlane(held, w) == r_sum);
+                for (int w = 0; w < WPB; ++w) first = first && !(w < wv && __builtin_amdgcn_readlane(held, w) == r_sum);
                 if (first) {
 #pragma unroll
-                    for (int w = 1; w < 8; ++w)
+                    for (int w = 1; w < WPB; ++w)
                         if (w > wv && __builtin_amdgcn_readlane(held, w) == r_sum) {
 #pragma unroll
                             for (int it = 0; it < IT; ++it) gacc.v[it] += *at(&s_row[w][it][0]);
@@ -798,7 +800,7 @@ __global__ __launch_bounds__(512, (IT <= 2 ? (KT == 10 ? 8 : 7) : 4)) void tripl
     if (wv == 0 && lz == 0) {
         double s = 0.0;
         for (int w = 0; w < wpb; ++w) s += sred[w];
-        ws.partials[blockIdx.x] = s;
+        *(PLAN ? plan_partial(ws, (int)blockIdx.x) : ws.partials + blockIdx.x) = s;
     }
 }
 
@@ -1296,16 +1298,20 @@ __device__ __forceinline__ void apply_relation_row(int64_t row, float *__restric
 }
 
 // The loss partials of the scoring kernel into *loss_accum by a whole block of 256 (add_loss_partials_wave of step_rows.h: by one
-// wave): every lane a strided share (all loads in flight), then a fixed tree
+// wave): every lane a strided share (all loads in flight), then a fixed tree.  n_partials <= kMaxPlanPartials, laid out by
+// plan_partial; the ones past kMaxBlocks are cleared once read (step_rows.h: that part of the workspace is zero between steps).
 __device__ __forceinline__ void add_loss_partials_block(const StepWs &ws, int n_partials, double *__restrict__ loss_accum) {
-    static_assert(kMaxBlocks <= 16 * 256, "the block reads 16 partials per lane");
+    constexpr int kPerLane = 32, kLow = kMaxBlocks / 256;
+    static_assert(kMaxPlanPartials <= kPerLane * 256 && kMaxBlocks % 256 == 0, "the block reads 32 partials per lane");
     __shared__ double sp[256];
-    double v[16];
+    double v[kPerLane];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) { const int i = u * 256 + (int)threadIdx.x; v[u] = i < n_partials ? ws.partials[i] : 0.0; }
+    for (int u = 0; u < kPerLane; ++u) { const int i = u * 256 + (int)threadIdx.x; v[u] = i < n_partials ? *plan_partial(ws, i) : 0.0; }
     double acc = 0.0;
 #pragma unroll
-    for (int u = 0; u < 16; ++u) acc += v[u];
+    for (int u = 0; u < kPerLane; ++u) acc += v[u];
+#pragma unroll
+    for (int u = kLow; u < kPerLane; ++u) { const int i = u * 256 + (int)threadIdx.x; if (i < n_partials) *plan_partial(ws, i) = 0.0; }
     sp[threadIdx.x] = acc;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -1577,8 +1583,11 @@ static bool step_wave_enabled() {
     return env != 0;
 }
 
+// triple_wave's launch: waves per workgroup and workgroups, decided by wave_geometry (below, next to wave_rule) and nowhere else
+struct WaveGeometry { int waves, grid; };
+
 template <int IT64>
-void launch_wave(int nb, int block, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
+void launch_wave(const WaveGeometry &g, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
                  int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, float *contrib = nullptr,
                  const uint32_t *pflags = nullptr, const uint32_t *order = nullptr) {
     const int k = cfg.neg_group_k;
@@ -1586,12 +1595,18 @@ void launch_wave(int nb, int block, hipStream_t st, const float *ent, const floa
 #define OEA_WAVE(L1, KT)                                                                                                               \
     do {                                                                                                                               \
         if constexpr (!oea::kDetScratch) {  /* PLAN = true: where a plan can exist (kPlanInstance) */                                  \
-            if (contrib) {                                                                                                             \
-                oea::launch_timed(triple_wave<IT64, L1, KT, true>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, order);   \
+            if (contrib) {  /* WPB = g.waves: 8 exists at ld <= 128 alone (wave_geometry gives ld > 128 four waves) */                  \
+                if constexpr (IT64 <= 2) {                                                                                             \
+                    if (g.waves == 8) {                                                                                                \
+                        oea::launch_timed(triple_wave<IT64, L1, KT, true, 8>, g.grid, 8 * 64, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, order);   \
+                        break;                                                                                                         \
+                    }                                                                                                                  \
+                }                                                                                                                      \
+                oea::launch_timed(triple_wave<IT64, L1, KT, true, 4>, g.grid, 4 * 64, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, order);   \
                 break;                                                                                                                 \
             }                                                                                                                          \
         }                                                                                                                              \
-        oea::launch_timed(triple_wave<IT64, L1, KT, false>, nb, block, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, nullptr);   \
+        oea::launch_timed(triple_wave<IT64, L1, KT, false>, g.grid, g.waves * 64, st, ent, rel, ld, pos, n_pos, neg, k, cfg, ws, dbg, contrib, pflags, nullptr);   \
     } while (0)
     if (k == 10) { if (cfg.l1) OEA_WAVE(1, 10); else OEA_WAVE(0, 10); }
     else { if (cfg.l1) OEA_WAVE(1, 0); else OEA_WAVE(0, 0); }
@@ -1615,6 +1630,22 @@ static bool wave_rule(const oea_step_cfg &cfg, int64_t n_ent, int64_t n_rel, int
            !step_runtime_kind();
 }
 
+// THE launch geometry of triple_wave, for launch_grouped's launch and for launch_step's count of the loss partials (one per
+// workgroup).  ld > 128: 4 waves, one workgroup per 4 positives.  ld <= 128 without a plan: 8 waves, one per 8 positives -- both
+// are loss_partials' count, the grid triple_grouped would take.  ld <= 128 with a plan: 4 waves, one workgroup per 4 positives, up to
+// kMaxPlanPartials of them (the grid-stride loop takes the rest): a 4-wave workgroup fits the slots that the side stream's
+// 256-thread workgroups (the epoch sampler's 49,600) leave one at a time, where an 8-wave workgroup needs two slots on every SIMD of
+// one CU at the same moment and waits for the sampler to end.  OEA_STEP_WAVE_BLOCK (A/B runs, ld <= 128, plan or
+// not): 512 = 8 waves per 8 positives, the geometry before this rule; 256 = 4 waves per 8 positives, two slots per wave.
+static WaveGeometry wave_geometry(int32_t ld, int64_t n_pos, bool planned) {
+    static const int blk_env = [] { const char *e = getenv("OEA_STEP_WAVE_BLOCK"); return e ? atoi(e) : 0; }();
+    const int per8 = std::max(loss_partials(ld, n_pos), 1);      // (per 4 at ld > 128)
+    if (ld > 128) return {4, per8};
+    if (blk_env == 256 || blk_env == 512) return {blk_env / 64, per8};
+    if (!planned) return {8, per8};
+    return {4, (int)std::min<int64_t>(std::max<int64_t>(oea::ceil_div(n_pos, 4), 1), kMaxPlanPartials)};
+}
+
 // The instances of for_row_width's ladder that wave_rule can send to triple_wave (ld <= 256), and with them the plan's: the kernels
 // of a planned step are built for these alone, and in the fp32 build alone (oea_step_plan_supported refuses the fixed-point build)
 template <int G, int IT>
@@ -1622,23 +1653,20 @@ constexpr bool kWaveInstance = (G == 32 && IT <= 4) || (G == 64 && IT == 4);
 template <int G, int IT>
 constexpr bool kPlanInstance = kWaveInstance<G, IT> && !oea::kDetScratch;
 
+// nb, block: triple_grouped's launch; where wave_rule sends the step to triple_wave, wave_geometry alone decides
 template <int G, int IT>
 void launch_grouped(int nb, int block, hipStream_t st, const float *ent, const float *rel, int ld, const int32_t *pos,
                     int64_t n_pos, const int32_t *neg, const oea_step_cfg &cfg, const StepWs &ws, bool wave, float *contrib = nullptr,
                     const uint32_t *pflags = nullptr, const uint32_t *order = nullptr) {
     const bool runtime_kind = step_runtime_kind();
     const int k = cfg.neg_group_k;
-    // one wave per positive (round 6) where wave_rule says so (wave = its answer; ld <= 256 are exactly the instances below): same
-    // grid as triple_grouped with blocks of (256 / G) waves, so the number of loss partials is launch_step's nb1 either way
+    // one wave per positive (round 6) where wave_rule says so (wave = its answer; ld <= 256 are exactly the instances below), in
+    // wave_geometry's workgroups: launch_step counts the loss partials by the same rule (a planned step: contrib != nullptr)
     if constexpr (kWaveInstance<G, IT>) {
         if (wave) {
             constexpr int IT64 = G == 32 ? (IT + 1) / 2 : 4;
-            // G == 32 (ld <= 128): the grid has one workgroup per 8 positives (launch_step's rule for the loss partials).  512 threads =
-            // one positive per wave; 256 threads = two per wave (grid stride): half the waves, nearly all resident at once, and
-            // 4-wave workgroups find their slots beside side-stream kernels where 8-wave workgroups starve (OEA_STEP_WAVE_BLOCK)
-            static const int blk_env = [] { const char *e = getenv("OEA_STEP_WAVE_BLOCK"); return e ? atoi(e) : 0; }();
-            const int wblock = G == 32 ? (blk_env == 256 || blk_env == 512 ? blk_env : 512) : (block / G) * 64;
-            launch_wave<IT64>(nb, wblock, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, contrib, pflags, order);
+            const WaveGeometry g = wave_geometry(ld, n_pos, contrib != nullptr);
+            launch_wave<IT64>(g, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, contrib, pflags, order);
             return;
         }
     }
@@ -1665,8 +1693,18 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
     const bool projected = transd || (transh && !transh_grouped);
     const bool grouped = transh_grouped || (!projected && cfg.neg_group_k > 0 && cfg.loss_kind != OEA_LOSS_MARGIN);
     const int64_t items = step_items(cfg, n_pos, n_neg);
-    const int n_part = loss_partials(ld, items);     // (G is for_row_width's: 32 up to ld 128, 64 beyond)
-    const int nb1 = std::max(n_part, 1);
+    // (G is for_row_width's: 32 up to ld 128, 64 beyond.)  A planned step is triple_wave's (oea_step_plan_supported asks wave_rule):
+    // one partial per workgroup of wave_geometry, up to kMaxPlanPartials and laid out by plan_partial (step_rows.h).  Only
+    // apply_step_plan's add_loss_partials_block reads that layout (and clears the partials past kMaxBlocks); add_loss_partials_wave
+    // of every other optimiser kernel reads ws.partials[0 .. n_part) -- so a planned step must end in apply_step_plan, which
+    // the SGD / Adagrad branch below does for every plan and which oea_step_plan_supported promises (no dense optimiser).
+    const bool planned_wave = plan && items > 0 && wave_rule(cfg, n_ent, n_rel, ld);
+    if (planned_wave && dense_opt) {
+        oea::set_error("a plan with a dense optimiser (opt_kind %d): its loss partials have no reader", (int)cfg.opt_kind);
+        return OEA_EUNSUPPORTED;
+    }
+    const int n_part = planned_wave ? wave_geometry(ld, n_pos, true).grid : loss_partials(ld, items);
+    const int nb1 = std::max(loss_partials(ld, items), 1);     // triple_grouped's and the other kernels' grid (launch_grouped's nb)
     // profiling events, 4 per STEP: [m0 fwd_bwd m1] ... [m2 apply m3], each pair attached to its kernel's dispatch
     // (oea::launch_timed); a GRAD call takes the first pair and decides whether the step is sampled, the APPLY call
     // that follows takes the second pair
@@ -1682,6 +1720,8 @@ int launch_step(float *ent, float *ent_acc, int64_t n_ent, float *rel, float *re
             // OEA_STEP_REL_ORDER=0 (A/B runs): a planned step's waves take the positives in batch order and every wave issues its own
             // relation row, as before the plan carried rel_order
             static const bool rel_order_on = [] { const char *e = getenv("OEA_STEP_REL_ORDER"); return !(e && e[0] == '0'); }();
+            // (plan->contrib != nullptr selects PLAN = true and the planned geometry there; with wave_rule it is planned_wave above
+            // -- a plan always carries contrib, and an empty batch launches one idle workgroup either way)
             launch_grouped<G, IT>(nb1, block, st, ent, rel, ld, pos, n_pos, neg, cfg, ws, wave_rule(cfg, n_ent, n_rel, ld),
                                   plan ? plan->contrib : nullptr, plan ? plan->pflags + plan_first_pos : nullptr,
                                   plan && rel_order_on ? plan->rel_order + plan_first_pos : nullptr);
